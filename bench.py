@@ -6,7 +6,10 @@ Cholesky(128)), fp64.  Data (y, X, gidx, Sigma) are shared variables resident in
 the timed region starts; the parameters (small) go in and the 6 outputs come out through
 the boundary on every step (both inside the timed region).
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR]
+
+``--dump-outputs DIR`` (e.g. the git-ignored ``bench_outputs/``) writes the six outputs of the last timed step (rank 0) as ``DIR/<name>.npy`` in fp64
+(``C4_OUTPUT_NAMES``); the inputs are seeded, so two builds run with the same arguments can be compared output for output.
 
 For N>1 the driver launches one rank per GPU with torch.distributed.run; started WITHOUT a launcher
 (``python bench.py --gpus N``, no WORLD_SIZE in the environment) the script starts its own N ranks the
@@ -254,7 +257,36 @@ def parse_args(argv=None):
     ap.add_argument("--single-stream", action="store_true", help="frozen plan without the two-stream fork")
     ap.add_argument("--hotpath", action="store_true", help="also run the 45-case hot_* sweep (cold + warm), the blocked Cholesky and the GP graph (minutes; detail file only)")
     ap.add_argument("--detail", default=None, help="where the full record goes (default: gpurun_out/bench_detail.json when gpurun_out/ exists, else bench_detail.json)")
-    return ap.parse_args(argv)
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the outputs of the last timed step (rank 0) as DIR/<name>.npy, fp64, for output-for-output comparison of two builds")
+    args = ap.parse_args(argv)
+    if args.steps < 1:
+        ap.error("--steps must be >= 1")
+    return args
+
+
+# the timed path's results, in the order both legs return them (oracle/ref_graphs.build_c4: logp, then its gradient
+# with respect to each parameter of configs.C4_PARAMS)
+C4_OUTPUT_NAMES = ("logp", "dlogp_dmu_g", "dlogp_dlog_tau", "dlogp_dz", "dlogp_dbeta", "dlogp_dlog_sigma")
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(outs, names, out_dir):
+    """``outs`` as ``out_dir/<name>.npy`` (float32 stays float32, every other dtype becomes float64).  The c4 outputs
+    are a scalar and four vectors of at most K or G entries, far below ``DUMP_LIMIT_BYTES``; exceeding it is an error."""
+    arrs = []
+    for a in outs:
+        a = np.asarray(a)
+        arrs.append(np.ascontiguousarray(a, dtype=np.float32 if a.dtype == np.float32 else np.float64))
+    if len(arrs) != len(names):
+        raise ValueError(f"{len(arrs)} outputs but {len(names)} names")
+    total = sum(a.nbytes for a in arrs)
+    if total > DUMP_LIMIT_BYTES:
+        raise ValueError(f"outputs hold {total} bytes, more than the {DUMP_LIMIT_BYTES}-byte dump limit")
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in zip(names, arrs):
+        np.save(os.path.join(out_dir, f"{name}.npy"), a)
+    return [os.path.join(out_dir, f"{n}.npy") for n in names]
 
 
 def measure(args):
@@ -307,11 +339,14 @@ def measure(args):
     replicas.barrier(dist)
     t0 = time.perf_counter()
     for _ in range(args.steps):
-        step()
+        last = step()
     ffi.check(lib.pthip_synchronize())
     elapsed = time.perf_counter() - t0
     replicas.barrier(dist)
     elapsed = replicas.max_over_ranks(dist, elapsed)
+    if args.dump_outputs and info.rank == 0:
+        # what the caller of the timed path received from its last step (inputs are seeded: configs.c4_inputs)
+        dump_outputs(last, C4_OUTPUT_NAMES, os.path.abspath(args.dump_outputs))
     fn_stats = None
     if fn is not None:
         exe_f = f.vm.jit_fn

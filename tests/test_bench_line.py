@@ -89,3 +89,35 @@ def test_default_run_skips_the_sweep():
     args = bench.parse_args([])
     assert args.gpus == 1 and not args.hotpath
     assert args.steps * 0.2e-3 < 60  # default K at ~0.2 ms per evaluation: seconds, not minutes
+
+
+def test_dump_outputs_writes_one_npy_per_output(tmp_path):
+    import numpy as np
+
+    outs = [np.float64(-1.5), np.arange(128.0), np.array(0.25), np.ones(128, np.float32), np.zeros(128), np.array(3.0)]
+    paths = bench.dump_outputs(outs, bench.C4_OUTPUT_NAMES, str(tmp_path / "d"))
+    assert [os.path.basename(p) for p in paths] == [f"{n}.npy" for n in bench.C4_OUTPUT_NAMES]
+    for a, p in zip(outs, paths):
+        b = np.load(p)
+        assert b.dtype == (np.float32 if np.asarray(a).dtype == np.float32 else np.float64)
+        np.testing.assert_array_equal(b, a)
+
+
+def test_dump_outputs_refuses_more_than_the_limit(tmp_path, monkeypatch):
+    import numpy as np
+    import pytest
+
+    monkeypatch.setattr(bench, "DUMP_LIMIT_BYTES", 1024)
+    with pytest.raises(ValueError):
+        bench.dump_outputs([np.zeros(1024)], ("x",), str(tmp_path))
+    assert not list(tmp_path.iterdir())
+
+
+def test_steps_sets_the_timed_steps_and_must_be_positive():
+    import pytest
+
+    a = bench.parse_args(["--steps", "7", "--warmup", "3", "--dump-outputs", "out"])
+    assert a.steps == 7 and a.warmup == 3 and a.dump_outputs == "out"
+    assert bench.parse_args([]).dump_outputs is None
+    with pytest.raises(SystemExit):
+        bench.parse_args(["--steps", "0"])

@@ -1,4 +1,4 @@
-"""CPU, build container only: the HipLinker boundary against the live reference."""
+"""CPU: the HipLinker boundary against the reference (its importable copy ``oracle/_ref``, built by ``build()``)."""
 import json
 import os
 
@@ -7,7 +7,7 @@ import pytest
 
 import make_ref
 
-pytestmark = pytest.mark.skipif(not make_ref.available(), reason="/root/reference not present (GPU box)")
+pytestmark = pytest.mark.skipif(not make_ref.importable(), reason="no importable reference copy (oracle/_ref not built: the reference was not found)")
 
 
 @pytest.fixture(scope="module")
