@@ -473,6 +473,44 @@ int pthip_comm_size(int* nranks, int* rank);
 int pthip_comm_destroy(void);
 int pthip_all_reduce(int dtype, int op, int64_t n, void* buf);
 
+/* ---- sparse matrices (pytensor.sparse csr / csc; csrc/sparse.hip) ------------------------------------
+ * A matrix is given as CSR arrays: `rows` rows of an (rows x n) matrix, data[nnz] (dtype), indices[nnz]
+ * and indptr[rows + 1] (int32); a csc matrix is the CSR of its transpose.  Indices need not be sorted
+ * and may repeat.  Every result is bit-reproducible (no floating-point atomics).  A column index out
+ * of range sets status bit 0 (pthip_check_status).  dtype: float32 / float64.
+ * exclusive_scan_i32: out[0..n] (n + 1 int32) = exclusive prefix sums of in[n], out[n] = total.
+ * csr_spmm: out[r, j] (strides so0, so1) = sum_e data[e] * B[indices[e], j] for j < k (B strides sb0, sb1;
+ *   B == NULL with k == 1: the row sums); lanes (1, 4, 16, 64): lanes per row when k == 1; has_long:
+ *   also run the workgroup-per-row pass for rows longer than 1024 entries (0 only if none exists).
+ * csr_transpose: the CSR arrays of the transpose (n rows; data_out / indices_out: nnz, indptr_out: n + 1),
+ *   a stable sort of the entries by column (row order kept within a column: scipy's tocsc() order).
+ * csr_sddmm: out[e] = (data ? data[e] : 1) * sum_{j<k} P[row(e), j] * Q[col(e), j].
+ * csr_gather: out[e] = data[e] * V[row(e) * s_major + col(e) * s_minor] (op 0) or data[e] + ... (op 1).
+ * csr_todense: out[r, c] (strides so0, so1) += entries in stored order (duplicates summed); with
+ *   accumulate == 0, out (contiguous, rows x n) is zero-filled first.
+ * csr_fromdense_count / _fill: the CSR arrays of the non-zeros of x (rows x n, strides sx0, sx1), sorted
+ *   indices: count writes indptr (rows + 1); the caller reads indptr[rows], allocates, then fills.
+ * csr_csm_grad: CSMGrad.perform (sparse/basic.py): out[e] = sum of the g entries in the row of x entry
+ *   e whose column equals its column. */
+int pthip_exclusive_scan_i32(int64_t n, const void* in, void* out);
+int pthip_csr_spmm(int dtype, int64_t rows, int64_t n, int64_t k, int64_t nnz, const void* data, const void* indices,
+                   const void* indptr, const void* B, int64_t sb0, int64_t sb1, void* out, int64_t so0, int64_t so1,
+                   int lanes, int has_long);
+int pthip_csr_transpose(int dtype, int64_t rows, int64_t n, int64_t nnz, const void* data, const void* indices,
+                        const void* indptr, void* data_out, void* indices_out, void* indptr_out);
+int pthip_csr_sddmm(int dtype, int64_t rows, int64_t n, int64_t k, int64_t nnz, const void* data, const void* indices,
+                    const void* indptr, const void* P, int64_t sp0, int64_t sp1, const void* Q, int64_t sq0, int64_t sq1,
+                    void* out);
+int pthip_csr_gather(int dtype, int op, int64_t rows, int64_t n, int64_t nnz, const void* data, const void* indices,
+                     const void* indptr, const void* V, int64_t s_major, int64_t s_minor, void* out);
+int pthip_csr_todense(int dtype, int64_t rows, int64_t n, int64_t nnz, const void* data, const void* indices,
+                      const void* indptr, void* out, int64_t so0, int64_t so1, int accumulate);
+int pthip_csr_fromdense_count(int dtype, int64_t rows, int64_t n, const void* x, int64_t sx0, int64_t sx1, void* indptr);
+int pthip_csr_fromdense_fill(int dtype, int64_t rows, int64_t n, const void* x, int64_t sx0, int64_t sx1, const void* indptr,
+                             void* data, void* indices);
+int pthip_csr_csm_grad(int dtype, int64_t rows, int64_t nnz_x, const void* x_indices, const void* x_indptr, int64_t nnz_g,
+                       const void* g_data, const void* g_indices, const void* g_indptr, void* out);
+
 #ifdef __cplusplus
 }
 #endif

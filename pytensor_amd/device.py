@@ -178,3 +178,60 @@ def copy_into(dst: DeviceArray, src: DeviceArray):
             dst.itemsize, nd, _i64arr(dst.shape), dst.ptr, _i64arr(dst.strides), src.ptr, _i64arr(sstr)
         )
     )
+
+
+class DeviceSparse:
+    """A pytensor.sparse matrix in HBM: the three arrays of a CSR matrix (``data``, int32 ``indices``, int32
+    ``indptr``) and a host-known logical ``shape``.  A csc matrix is held as the CSR of its transpose in the same
+    three arrays — exactly scipy's csc arrays — so ``Transpose`` is a change of ``format`` and nothing else.
+    ``major`` / ``minor``: the row / column count of the stored CSR.  ``max_row``: the longest stored row when
+    the host knows it (inputs, constants), else None.  ``cache``: per-value derived operands (the transpose of a
+    constant is built once and kept here, with the constant)."""
+
+    __slots__ = ("data", "indices", "indptr", "shape", "format", "max_row", "cache")
+
+    def __init__(self, data, indices, indptr, shape, format, max_row=None):
+        self.data, self.indices, self.indptr = data, indices, indptr
+        self.shape = (int(shape[0]), int(shape[1]))
+        self.format = str(format)
+        self.max_row = max_row
+        self.cache = {}
+
+    @property
+    def major(self) -> int:
+        return self.shape[0] if self.format == "csr" else self.shape[1]
+
+    @property
+    def minor(self) -> int:
+        return self.shape[1] if self.format == "csr" else self.shape[0]
+
+    @property
+    def nnz(self) -> int:
+        return self.data.size
+
+    @property
+    def dtype(self):
+        return self.data.dtype
+
+    ndim = 2
+
+    @classmethod
+    def from_host(cls, m) -> "DeviceSparse":
+        """a scipy csr_matrix / csc_matrix, uploaded as given (unsorted indices and duplicates kept)"""
+        if m.format not in ("csr", "csc"):
+            raise NotImplementedError(f"hip linker: sparse format {m.format!r} (only csr and csc are supported)")
+        indptr = np.asarray(m.indptr, dtype=np.int32)
+        rows = np.diff(indptr)
+        return cls(DeviceArray.from_host(np.asarray(m.data)), DeviceArray.from_host(np.asarray(m.indices, dtype=np.int32)),
+                   DeviceArray.from_host(indptr), m.shape, m.format, int(rows.max()) if rows.size else 0)
+
+    def to_host(self):
+        import scipy.sparse as sp
+
+        ffi.check(ffi.lib().pthip_synchronize())
+        cls = sp.csr_matrix if self.format == "csr" else sp.csc_matrix
+        return cls((self.data.to_host(sync=False), self.indices.to_host(sync=False), self.indptr.to_host(sync=True)),
+                   shape=self.shape, copy=False)
+
+    def __repr__(self):
+        return f"DeviceSparse({self.format}, shape={self.shape}, nnz={self.nnz}, dtype={self.dtype})"

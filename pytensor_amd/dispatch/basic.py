@@ -11,7 +11,7 @@ from __future__ import annotations
 
 import numpy as np
 
-from pytensor_amd.device import DeviceArray, contiguous_strides, copy_into
+from pytensor_amd.device import DeviceArray, DeviceSparse, contiguous_strides, copy_into
 from pytensor_amd.dispatch import handler
 from pytensor_amd.executor import HOST_MAX, HostValue
 
@@ -80,6 +80,8 @@ def deep_copy(node, inputs, env):
     (x,) = inputs
     if isinstance(x, HostValue):
         return [HostValue(x.a.copy())]
+    if isinstance(x, DeviceSparse):  # (no kernel writes a sparse value in place; the exit D2H is the copy)
+        return [x]
     out = DeviceArray.empty(x.shape, x.dtype)
     copy_into(out, x)
     return [out]

@@ -32,7 +32,7 @@ import weakref
 import numpy as np
 
 from pytensor_amd import coherence, ffi
-from pytensor_amd.device import DeviceArray
+from pytensor_amd.device import DeviceArray, DeviceSparse
 from pytensor_amd.ir import Graph
 
 HOST_MAX = 64  # host-resident values are tiny integer/bool arrays (shape math)
@@ -374,7 +374,11 @@ class HipExecutable:
         self.has_rng = any(v.kind == "rng" for v in self.graph.vars.values())
         # an all-reduce drains the stream and runs on RCCL's: not capturable either
         self.has_collective = _has_op(self.graph, "AllReduce")
-        if self.has_rng or self.has_collective:
+        # sparse graph inputs / outputs: the nnz of a sparse input is part of its value, and a frozen plan's
+        # staging block has a fixed geometry — such graphs stay eager (a changed nnz can never replay a stale
+        # plan).  Sparse constants are uploaded once and freeze like dense ones (the CAR case).
+        self.has_sparse_io = any(self.graph.vars[v].kind == "sparse" for v in (*self.graph.inputs, *self.graph.outputs))
+        if self.has_rng or self.has_collective or self.has_sparse_io:
             self.auto_freeze = False
         self._handlers = dispatch.HANDLERS
         self._resident_cache = {}  # input position -> ResidentEntry
@@ -460,6 +464,9 @@ class HipExecutable:
             return self._const_cache[vid]
         if v.const is None and v.kind == "tensor":  # (a NoneConst argument is a constant whose value IS None)
             raise KeyError(f"hip linker: variable {vid} ({v.name}) has no value yet and is not a constant")
+        if v.kind == "sparse":  # uploaded once per executable; derived operands are cached with it (DeviceSparse.cache)
+            val = self._const_cache[vid] = DeviceSparse.from_host(v.const)
+            return val
         a = np.asarray(v.const)
         if v.kind != "tensor" or a.size <= HOST_MAX:
             # small constants (alpha/beta of Gemv, fill values, shapes) stay on the host and
@@ -479,6 +486,8 @@ class HipExecutable:
             from pytensor_amd.rng import RngState
 
             return RngState.from_generator(value)
+        if var.kind == "sparse":
+            return self._sparse_input(pos, var, value)
         if var.kind != "tensor":
             return HostValue(np.asarray(value))
         a = np.asarray(value)
@@ -496,6 +505,20 @@ class HipExecutable:
         dev = DeviceArray.from_host(a)
         env.keepalive.append(a)
         return dev
+
+    def _sparse_input(self, pos, var, value):
+        import scipy.sparse as sp
+
+        if isinstance(value, DeviceSparse):
+            return value
+        if not sp.issparse(value) or value.format != var.format:
+            raise TypeError(f"input {pos} ({var.name}): expected a scipy {var.format}_matrix, got {type(value).__name__}")
+        if str(value.dtype) != var.dtype:
+            raise TypeError(f"input {pos} ({var.name}): expected dtype {var.dtype}, got {value.dtype}")
+        for d, s in enumerate(var.shape):
+            if s is not None and value.shape[d] != s:
+                raise TypeError(f"input {pos} ({var.name}): static shape {var.shape} violated by {value.shape}")
+        return DeviceSparse.from_host(value)
 
     def _refresh_resident(self, pos, value, a=None, env=None) -> DeviceArray:
         """Device copy of resident input ``pos`` for the host value in the storage cell: reused
@@ -774,6 +797,8 @@ class HipExecutable:
             var = self.graph.vars[vid]
             if var.kind == "rng":  # the advanced generator, as a numpy Generator(Philox) again
                 host.append(o.to_generator())
+            elif isinstance(o, DeviceSparse):  # a scipy matrix of the output type's format
+                host.append(o.to_host())
             elif isinstance(o, HostValue):
                 host.append(np.array(o.a, dtype=var.dtype if var.kind == "tensor" else o.a.dtype, copy=True))
             else:

@@ -165,6 +165,15 @@ SIGNATURES = {
     "pthip_all_reduce": (_int, [_int, _int, _i64, _vp]),
     "pthip_check_status": (_int, [C.POINTER(_int)]),
     "pthip_status_ptr": (_vp, []),
+    "pthip_exclusive_scan_i32": (_int, [_i64, _vp, _vp]),
+    "pthip_csr_spmm": (_int, [_int, _i64, _i64, _i64, _i64, _vp, _vp, _vp, _vp, _i64, _i64, _vp, _i64, _i64, _int, _int]),
+    "pthip_csr_transpose": (_int, [_int, _i64, _i64, _i64, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "pthip_csr_sddmm": (_int, [_int, _i64, _i64, _i64, _i64, _vp, _vp, _vp, _vp, _i64, _i64, _vp, _i64, _i64, _vp]),
+    "pthip_csr_gather": (_int, [_int, _int, _i64, _i64, _i64, _vp, _vp, _vp, _vp, _i64, _i64, _vp]),
+    "pthip_csr_todense": (_int, [_int, _i64, _i64, _i64, _vp, _vp, _vp, _vp, _i64, _i64, _int]),
+    "pthip_csr_fromdense_count": (_int, [_int, _i64, _i64, _vp, _i64, _i64, _vp]),
+    "pthip_csr_fromdense_fill": (_int, [_int, _i64, _i64, _vp, _i64, _i64, _vp, _vp, _vp]),
+    "pthip_csr_csm_grad": (_int, [_int, _i64, _i64, _vp, _vp, _i64, _vp, _vp, _vp, _vp]),
     "pthip_set_safe_mode": (_int, [_int]),
 }
 

@@ -28,9 +28,10 @@ class Var:
     id: int
     dtype: str
     shape: tuple  # static shape, ``None`` for unknown dims (TensorType.shape)
-    kind: str = "tensor"  # "tensor" | "scalar" (ScalarType) | "slice" | "none"
-    const: np.ndarray | None = None
+    kind: str = "tensor"  # "tensor" | "scalar" (ScalarType) | "slice" | "none" | "rng" | "sparse"
+    const: np.ndarray | None = None  # (kind "sparse": a scipy.sparse csr_matrix / csc_matrix)
     name: str | None = None
+    format: str | None = None  # kind "sparse": "csr" | "csc" (SparseTensorType.format)
 
     @property
     def ndim(self) -> int:
@@ -54,9 +55,9 @@ class Graph:
     name: str = "graph"
 
     # -- construction ------------------------------------------------------
-    def new_var(self, dtype, shape, kind="tensor", const=None, name=None) -> int:
+    def new_var(self, dtype, shape, kind="tensor", const=None, name=None, format=None) -> int:
         vid = len(self.vars)
-        self.vars[vid] = Var(vid, str(dtype), tuple(shape), kind, const, name)
+        self.vars[vid] = Var(vid, str(dtype), tuple(shape), kind, const, name, format)
         return vid
 
     def add_node(self, op, params, inputs, outputs) -> Node:
@@ -140,18 +141,38 @@ def decode_array(d: dict) -> np.ndarray:
     return arr.reshape(d["shape"])
 
 
+def encode_sparse(m) -> dict:
+    """a scipy csr / csc matrix as its three arrays and its shape (stored as given: unsorted indices and
+    duplicate entries survive the round trip)"""
+    return {"format": m.format, "shape": [int(s) for s in m.shape], "data": encode_array(m.data),
+            "indices": encode_array(m.indices), "indptr": encode_array(m.indptr)}
+
+
+def decode_sparse(d: dict):
+    import scipy.sparse as sp
+
+    cls = {"csr": sp.csr_matrix, "csc": sp.csc_matrix}[d["format"]]
+    arrays = (decode_array(d["data"]), decode_array(d["indices"]), decode_array(d["indptr"]))
+    return cls(arrays, shape=tuple(d["shape"]), copy=False)
+
+
 def _var_to_dict(v: Var) -> dict:
     d = {"id": v.id, "dtype": v.dtype, "shape": list(v.shape), "kind": v.kind}
     if v.name:
         d["name"] = v.name
+    if v.format:
+        d["format"] = v.format
     if v.const is not None:
-        d["const"] = encode_array(v.const)
+        d["const"] = encode_sparse(v.const) if v.kind == "sparse" else encode_array(v.const)
     return d
 
 
 def _var_from_dict(d: dict) -> Var:
-    const = decode_array(d["const"]) if "const" in d else None
-    return Var(d["id"], d["dtype"], tuple(d["shape"]), d.get("kind", "tensor"), const, d.get("name"))
+    kind = d.get("kind", "tensor")
+    const = None
+    if "const" in d:
+        const = decode_sparse(d["const"]) if kind == "sparse" else decode_array(d["const"])
+    return Var(d["id"], d["dtype"], tuple(d["shape"]), kind, const, d.get("name"), d.get("format"))
 
 
 def _params_to_json(p):

@@ -53,6 +53,7 @@ from pytensor.tensor.subtensor import (
 from pytensor.tensor.random.op import RandomVariable
 from pytensor.tensor.random.type import RandomType
 from pytensor.tensor.type import TensorType
+from pytensor.sparse.type import SparseTensorType
 from pytensor.tensor.type_other import NoneTypeT, SliceType
 
 from pytensor_amd.ir import Graph
@@ -589,6 +590,9 @@ def _(op, node, ctx):
 
 def _var_spec(v):
     t = v.type
+    if isinstance(t, SparseTensorType):  # (a TensorType subclass: checked first)
+        _check_sparse_type(t)
+        return str(t.dtype), tuple(t.shape), "sparse"
     if isinstance(t, TensorType):
         return str(t.dtype), tuple(t.shape), "tensor"
     if isinstance(t, ScalarType):
@@ -746,6 +750,91 @@ def _register_ofg():
 _register_ofg()
 
 
+_SPARSE_DTYPES = ("float32", "float64")
+
+
+def _check_sparse_type(t):
+    """csr / csc of float32 / float64 only (indices and indptr are int32, as CSM requires)"""
+    if t.format not in ("csr", "csc"):
+        raise NotImplementedError(f"hip linker: sparse format {t.format!r} is not supported (only csr and csc)")
+    if str(t.dtype) not in _SPARSE_DTYPES:
+        raise NotImplementedError(f"hip linker: sparse dtype {t.dtype} is not supported (only float32 and float64)")
+
+
+def _register_sparse():
+    # pytensor.sparse csr / csc: kernels in csrc/sparse.hip, handlers in dispatch/sparse.py (DESIGN §4, §7).
+    # `mode="hip"` excludes the `cxx_only` rewrites (HipLinker.incompatible_rewrites), so the C-only
+    # specialisations (MulSDCSR, StructuredDotCSR, AddSD_ccode, ...) never reach the lowering.
+    import pytensor.sparse.basic as sb
+    import pytensor.sparse.math as sm
+
+    def _is_sparse(v):
+        from pytensor.sparse.type import SparseTensorType
+
+        return isinstance(v.type, SparseTensorType)
+
+    for cls in (sb.CSMProperties, sb.CSMGrad, sb.DenseFromSparse, sm.StructuredDotGradCSR,
+                sm.StructuredDotGradCSC, sm.SamplingDot, sm.SparseDenseMultiply, sm.SparseDenseVectorMultiply,
+                sm.AddSD, sm.StructuredAddSV, sb.ColScaleCSC, sb.RowScaleCSC):
+        hip_funcify.register(cls)(lambda op, node, ctx: (type(op).__name__, {}))
+
+    @hip_funcify.register(sb.CSM)
+    def _(op, node, ctx):
+        return "CSM", {"format": str(op.format)}
+
+    @hip_funcify.register(sb.SparseFromDense)
+    def _(op, node, ctx):
+        return "SparseFromDense", {"format": str(op.format)}
+
+    @hip_funcify.register(sb.Transpose)
+    def _(op, node, ctx):
+        return "SparseTranspose", {}
+
+    @hip_funcify.register(sb.Cast)
+    def _(op, node, ctx):
+        return "SparseCast", {"out_type": str(op.out_type)}
+
+    @hip_funcify.register(sm.SpSum)
+    def _(op, node, ctx):
+        return "SpSum", {"axis": None if op.axis is None else int(op.axis)}
+
+    def _dense_and_sparse(op, node):
+        if node is not None and all(_is_sparse(v) for v in node.inputs):
+            raise NotImplementedError(f"hip linker: {type(op).__name__} of two sparse operands (sparse x sparse) is not lowered")
+
+    @hip_funcify.register(sm.Dot)
+    def _(op, node, ctx):
+        _dense_and_sparse(op, node)
+        return "SparseDot", {}
+
+    @hip_funcify.register(sm.TrueDot)
+    def _(op, node, ctx):
+        _dense_and_sparse(op, node)
+        if node is not None and not _is_sparse(node.inputs[0]):
+            raise NotImplementedError("hip linker: TrueDot with a dense left operand is not lowered")
+        return "TrueDot", {}
+
+    @hip_funcify.register(sm.StructuredDot)
+    def _(op, node, ctx):
+        _dense_and_sparse(op, node)
+        return "StructuredDot", {}
+
+    refused = [sm.AddSS, sm.AddSSData, sm.SparseSparseMultiply, sm.Usmm, sb.GetItemList, sb.GetItemListGrad, sb.GetItem2Lists,
+               sb.GetItem2ListsGrad, sb.GetItem2d, sb.GetItemScalar, sb.HStack, sb.VStack, sb.ConstructSparseFromList,
+               sb.Remove0, sb.EnsureSortedIndices, sb.Diag]
+    refused += [getattr(sm, n) for n in dir(sm) if n.endswith(("SS", "SD")) and n.startswith(
+        ("Equal", "NotEqual", "LessThan", "GreaterThan", "LessEqual", "GreaterEqual"))]
+
+    def _refuse(op, node, ctx):
+        raise NotImplementedError(f"hip linker: the sparse op {type(op).__name__} is not lowered (DESIGN §7)")
+
+    for cls in refused:
+        hip_funcify.register(cls)(_refuse)
+
+
+_register_sparse()
+
+
 def lower_fgraph(fgraph, name="graph", allow_host_fallback=False) -> Graph:
     g = Graph(name=name)
 
@@ -761,7 +850,11 @@ def lower_fgraph(fgraph, name="graph", allow_host_fallback=False) -> Graph:
                     shape = const.shape
                 elif kind == "slice":
                     const = v.data
-            i = g.new_var(dtype, shape, kind=kind, const=const, name=getattr(v, "name", None))
+                elif kind == "sparse":
+                    const = v.data  # (scipy csr_matrix / csc_matrix; ir.encode_sparse)
+                    shape = const.shape
+            fmt = v.type.format if kind == "sparse" else None
+            i = g.new_var(dtype, shape, kind=kind, const=const, name=getattr(v, "name", None), format=fmt)
             scope[v] = i
             return i
 
