@@ -753,8 +753,11 @@ PT_DEV float pt_betaincinv(float a, float b, float p) { return (float)pt_betainc
 
 _OPTIONAL_HELPERS = {"NdtriExp": ("ndtriexp",), "GammaInc": ("gammainc",), "GammaIncC": ("gammainc",), "BetaInc": ("betainc",), "PolyGamma": ("polygamma",),
                      "GammaIncInv": ("gammainc", "gammaincinv"), "GammaIncCInv": ("gammainc", "gammaincinv"),
-                     "BetaIncInv": ("betainc", "betaincinv")}
-_OPTIONAL_ORDER = ("gammainc", "betainc", "polygamma", "ndtriexp", "gammaincinv", "betaincinv")
+                     "BetaIncInv": ("betainc", "betaincinv"),
+                     "Jv": ("bessel",), "Ive": ("bessel",), "Kve": ("bessel",), "Owens_t": ("owens_t",)}
+_OPTIONAL_ORDER = ("gammainc", "betainc", "polygamma", "ndtriexp", "gammaincinv", "betaincinv", "bessel", "owens_t")
+# helpers kept as headers under csrc/ (the host accuracy tests compile the same text)
+_OPTIONAL_FILES = {"bessel": "special_bessel.h", "owens_t": "special_owens_t.h"}
 _optional_src_cache = {}
 
 
@@ -763,6 +766,9 @@ def _optional_src(key: str) -> str:
         if key == "gammainc":
             logfs, loghs = _gamma_tables()
             _optional_src_cache[key] = _c_table("pt_g_logfs", logfs) + _c_table("pt_g_loghs", loghs) + _GAMMAINC_SRC
+        elif key in _OPTIONAL_FILES:
+            with open(os.path.join(_HERE, "csrc", _OPTIONAL_FILES[key])) as f:
+                _optional_src_cache[key] = f.read()
         else:
             _optional_src_cache[key] = {"betainc": _BETAINC_SRC, "polygamma": _POLYGAMMA_SRC, "ndtriexp": _NDTRIEXP_SRC, "gammaincinv": _GAMMAINCINV_SRC,
                                         "betaincinv": _BETAINCINV_SRC}[key]
@@ -1018,6 +1024,12 @@ SCALAR_EXPR = {
     "J1": lambda a, i, o: f"({CTYPE[o]})j1((double){a[0]})",
     "I0": lambda a, i, o: f"({CTYPE[o]})cyl_bessel_i0((double){a[0]})",
     "I1": lambda a, i, o: f"({CTYPE[o]})cyl_bessel_i1((double){a[0]})",
+    # real-order Bessel functions and Owen's T: the reference evaluates scipy.special.jv / ive / kve / owens_t
+    # (scalar/math.py); fp64 helpers of csrc/special_bessel.h and csrc/special_owens_t.h, rounded for float32
+    "Jv": _helper("pt_jv"),
+    "Ive": _helper("pt_ive"),
+    "Kve": _helper("pt_kve"),
+    "Owens_t": _helper("pt_owens_t"),
     "Reciprocal": lambda a, i, o: f"(({CTYPE[o]})1 / ({CTYPE[o]}){a[0]})",
     "Maximum": _maxmin("pt_max"),  # 1744
     "Minimum": _maxmin("pt_min"),  # 1790
