@@ -511,6 +511,24 @@ int pthip_csr_fromdense_fill(int dtype, int64_t rows, int64_t n, const void* x, 
 int pthip_csr_csm_grad(int dtype, int64_t rows, int64_t nnz_x, const void* x_indices, const void* x_indptr, int64_t nnz_g,
                        const void* g_data, const void* g_indices, const void* g_indptr, void* out);
 
+/* ---- Discrete algebraic Riccati equation (csrc/riccati.hip; SolveDiscreteARE, linalg/solvers/linear_control.py) ----
+ * dare: X (batch, m, m) = the stabilising solution of A^T X A - X - A^T X B (R + B^T X B)^-1 B^T X A + Q = 0 for
+ *   contiguous A (batch, m, m), B (batch, m, n), Q (batch, m, m), R (batch, n, n), by the doubling algorithm, one
+ *   workgroup per item, computed in fp64; X in out_dtype.  0 <= n <= m <= 64.  No convergence within the step cap, a non-finite value
+ *   or a zero pivot of R or of a step's W gives an all-NaN X.  steps (int32[batch], may be NULL): the doubling steps
+ *   taken, -1 on failure.  ws: pthip_dare_workspace(batch, m, n) bytes of device memory (NULL when that is 0).
+ * dare_guard: the composed tier's guard before an LU: M (fp64 n x n) with a non-finite entry, or any M once *flag
+ *   is set, becomes the identity and sets *flag (int32; first != 0 starts it clear).
+ * dare_finish: the composed tier's last step.  H, dH (the last increment), A0 and Ak: fp64 m x m.  X (dtype) =
+ *   (H + H^T) / 2 when max|dH| <= m eps max|H|, max|Ak| <= sqrt(eps) max|A0|, all are finite and *flag is 0,
+ *   else NaN. */
+size_t pthip_dare_workspace(int64_t batch, int64_t m, int64_t n);
+int pthip_dare(int dtype, int out_dtype, int64_t batch, int64_t m, int64_t n, const void* A, const void* B, const void* Q, const void* R,
+               void* X, void* steps, void* ws, size_t ws_bytes);
+int pthip_dare_guard(int64_t n, void* M, void* flag, int first);
+int pthip_dare_finish(int dtype, int64_t m, const void* H, const void* dH, const void* A0, const void* Ak, const void* flag,
+                      void* X);
+
 #ifdef __cplusplus
 }
 #endif

@@ -26,6 +26,10 @@ namespace {
 constexpr int BLOCK = 256;
 
 template <class T> __device__ __forceinline__ T dev_abs(T x) { return x < T(0) ? -x : x; }
+// |x| for the pivot searches, with NaN ranked as +inf: every row still in the search is a candidate (a column of NaN
+// would otherwise leave none, and the "no candidate" key would index past the matrix), and a NaN pivot carries the
+// NaN into the factors as LAPACK's idamax-based getrf does
+template <class T> __device__ __forceinline__ T pivot_abs(T x) { return x != x ? T(INFINITY) : dev_abs(x); }
 
 template <class T>
 __global__ __launch_bounds__(BLOCK) void getrf_kernel(T* __restrict__ LUout,
@@ -57,7 +61,7 @@ __global__ __launch_bounds__(BLOCK) void getrf_kernel(T* __restrict__ LUout,
     T best = T(-1);
     int bi = k;
     for (int i = k + tid; i < n; i += BLOCK) {
-      const T v = dev_abs(W[i * ld + k]);
+      const T v = pivot_abs(W[i * ld + k]);
       if (v > best) { best = v; bi = i; }
     }
 #pragma unroll
@@ -195,7 +199,7 @@ __global__ __launch_bounds__(BLOCK) void getrf_reg_kernel(T* __restrict__ LUout,
       if (rho < n) {
         const int p = s_pos[rho];
         if (p >= k) {
-          const T x = dev_abs(col[rho]);
+          const T x = pivot_abs(col[rho]);
           const int ky = p * 256 + rho;
           if (x > v || (x == v && ky < key)) { v = x; key = ky; }
         }
@@ -394,7 +398,7 @@ __global__ __launch_bounds__(BLOCK) void lu_panel_kernel(T* __restrict__ W, long
     if (j < pw) {  // (uniform: the last panel may be narrower)
     const int k = k0 + j;
     // ---- this workgroup's candidate: largest |a_ik| among its rows i >= k, first such row
-    T v = (have && grow >= k) ? dev_abs(a[j]) : T(-1);
+    T v = (have && grow >= k) ? pivot_abs(a[j]) : T(-1);
     int key = (have && grow >= k) ? (int)grow : 0x7fffffff;
     wave_argmax<T>(v, key);
     if (lane == 63) { s_val[wid] = v; s_row[wid] = key; }
@@ -750,7 +754,7 @@ __global__ __launch_bounds__(TB) void lu_panel2_kernel(T* __restrict__ W, long l
       const unsigned long long tag = LU_MAGIC ^ ((unsigned long long)(k + 1) * LU_EPOCH_MUL) ^ nonce;
       // ---- A: this workgroup's candidate: largest |a_ik| among its rows not yet pivoted, first in the current order
       const bool act = have && !done;
-      T v = act ? dev_abs(a[0]) : T(-1);
+      T v = act ? pivot_abs(a[0]) : T(-1);
       int key = act ? cur : 0x7fffffff;
       wave_argmax<T>(v, key);
       const int wkey = __builtin_amdgcn_readlane(key, 63);
@@ -819,7 +823,7 @@ __global__ __launch_bounds__(TB) void lu_panel2_kernel(T* __restrict__ W, long l
               if (base + g * NPOLL < nW) {  // (uniform)
                 T x;
                 lu_from_bits(lane_bcast_u64<2>(b0[g]), x);  // entry 0 of the candidate row: its column-k value
-                x = dev_abs(x);
+                x = pivot_abs(x);
                 const int r = (int)lane_bcast_u64<0>(b0[g]);
                 if (r != 0x7fffffff && (x > cv || (x == cv && r < cr))) { cv = x; cr = r; best0 = b0[g]; best1 = b1[g]; }
               }

@@ -189,6 +189,10 @@ def blockwise(node, inputs, env):
         from pytensor_amd.dispatch import lu
 
         return lu.eigh(type("_N", (), {"params": cp}), ins, env)
+    if p["core_op"] == "SolveDiscreteARE":  # (one launch for the whole batch up to m = 64)
+        from pytensor_amd.dispatch import riccati
+
+        return [riccati.dare_device(env, *ins, riccati.out_dtype(env, node))]
     return _blockwise_loop(node, ins, env, inputs)
 
 

@@ -153,6 +153,10 @@ SIGNATURES = {
     "pthip_logsumexp_rows": (_int, [_int, _i64, _i64, _vp, _vp]),
     "pthip_logsumexp_rows_max": (_i64, [_int]),
     "pthip_colstat_workspace": (_sz, [_int, _i64, _i64, _i64]),
+    "pthip_dare_workspace": (_sz, [_i64, _i64, _i64]),
+    "pthip_dare": (_int, [_int, _int, _i64, _i64, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _sz]),
+    "pthip_dare_guard": (_int, [_i64, _vp, _vp, _int]),
+    "pthip_dare_finish": (_int, [_int, _i64, _vp, _vp, _vp, _vp, _vp, _vp]),
     "pthip_logsumexp_cols": (_int, [_int, _i64, _i64, _i64, _vp, _vp, _vp, _sz]),
     "pthip_softmax_cols": (_int, [_int, _int, _i64, _i64, _i64, _vp, _vp, _vp, _sz]),
     "pthip_cumulative": (_int, [_int, _int, _i64, _i64, _i64, _vp, _vp]),

@@ -731,12 +731,18 @@ _register_ifelse()
 
 def _register_ofg():
     from pytensor.compile.builders import OpFromGraph
-    from pytensor.tensor.linalg.solvers.linear_control import SolveSylvester
+    from pytensor.tensor.linalg.solvers.linear_control import SolveDiscreteARE, SolveSylvester
 
     @hip_funcify.register(SolveSylvester)
     def _(op, node, ctx):
         # (its inner graph is Schur + TRSYL, which have no lowering: the equation is solved directly)
         return "SolveSylvester", {}
+
+    @hip_funcify.register(SolveDiscreteARE)
+    def _(op, node, ctx):
+        # (its inner graph is QR + QZ(sort="iuc"), which has no lowering: the stabilising solution is computed
+        #  by the doubling algorithm instead, dispatch/riccati.py)
+        return "SolveDiscreteARE", {}
 
     @hip_funcify.register(OpFromGraph)
     def _(op, node, ctx):
