@@ -529,6 +529,20 @@ int pthip_dare_guard(int64_t n, void* M, void* flag, int first);
 int pthip_dare_finish(int dtype, int64_t m, const void* H, const void* dH, const void* A0, const void* Ak, const void* flag,
                       void* X);
 
+/* ---- Sylvester equation by Bartels-Stewart (csrc/sylvester.hip; SolveSylvester above the Kronecker tier) ----
+ * A X + X B = C for a batch of items, 1 <= m, n <= 1024, fp64 inside whatever the operand dtype:
+ *   real_schur: the real Schur forms A = U R U^T and B = V S V^T, one workgroup per form.  A (batch, m, m) and B
+ *     (batch, n, n) contiguous, of dtype.  b_is_a_t: B = A^T (m = n; B is not read and may be NULL): only A is
+ *     factored.  ws: pthip_sylvester_workspace(batch, m, n, b_is_a_t) bytes, laid out as fp64 [for each item b:
+ *     R_b (m x m), U_b^T (m x m)], then (unless b_is_a_t) [for each item: S_b (n x n), V_b^T (n x n)], then int32
+ *     info[batch][forms]: 0, -1 for a non-finite operand, or > 0 when the QR iteration reached its cap.
+ *   trsyl: F (fp64, batch x m x n, contiguous) <- Y with R Y + Y op(S) = F (op(S) = R^T when b_is_a_t), all NaN for an
+ *     item with a non-zero info.  The caller forms F = U^T C V before and X = U Y V^T after. */
+size_t pthip_sylvester_workspace(int64_t batch, int64_t m, int64_t n, int b_is_a_t);
+int pthip_real_schur(int dtype, int64_t batch, int64_t m, int64_t n, int b_is_a_t, const void* A, const void* B, void* ws,
+                     size_t ws_bytes);
+int pthip_trsyl(int64_t batch, int64_t m, int64_t n, int b_is_a_t, void* F, void* ws, size_t ws_bytes);
+
 #ifdef __cplusplus
 }
 #endif

@@ -433,16 +433,84 @@ def _ew1(env, body_ops, ins, in_dtypes, out_dtype, shape):
 
 # ---- Sylvester equation -----------------------------------------------------------------------------
 MAX_SYLVESTER = 4096  # m * n: the Kronecker system is (m n) x (m n)
+MAX_SYLVESTER_SCHUR = 1024  # m and n of the Bartels-Stewart tier (csrc/sylvester.hip SYL_MAX_N)
+
+
+def sylvester_tier(m: int, n: int):
+    """The tier that solves an m x n Sylvester equation: "kronecker" up to m n = 4096, "schur" (Bartels-Stewart)
+    above that up to m, n <= 1024, None (refused) beyond."""
+    if m * n <= MAX_SYLVESTER:
+        return "kronecker"
+    if max(m, n) <= MAX_SYLVESTER_SCHUR:
+        return "schur"
+    return None
+
+
+def _sylvester_refused(m, n):
+    return NotImplementedError(f"hip linker: SolveSylvester with m = {m}, n = {n} (device tiers: m*n <= {MAX_SYLVESTER} "
+                               f"Kronecker, m, n <= {MAX_SYLVESTER_SCHUR} Bartels-Stewart)")
+
+
+def solve_sylvester_schur(env, A, B, C, b_is_a_t=False, out_dtype=None):
+    """X (*batch, m, n) with A X + X B = C for operands with broadcastable leading batch dims, by Bartels-Stewart
+    (csrc/sylvester.hip): real Schur forms A = U R U^T, B = V S V^T in one launch (one workgroup per form), F = U^T C V
+    on the GEMM, R Y + Y S = F in a second launch, X = U Y V^T on the GEMM; fp64 throughout, X in ``out_dtype``
+    (default: the operands' working type).  ``b_is_a_t``: B = A^T, so only A is factored and R Y + Y R^T = U^T C U
+    is solved.  An item whose A or B holds a non-finite value, or whose QR iteration reached its cap, is all NaN.
+    No host read."""
+    from pytensor_amd.dispatch.blas import gemm_device
+    from pytensor_amd.dispatch.elemwise import _cast
+    from pytensor_amd.dispatch.linalg import _batchify, _lapack_operands
+
+    A, B, C = _lapack_operands(env, "SolveSylvester", A, B, C)
+    m, n = A.shape[-1], B.shape[-1]
+    if A.shape[-2:] != (m, m) or B.shape[-2:] != (n, n) or C.shape[-2:] != (m, n):
+        raise ValueError(f"SolveSylvester: incompatible shapes {A.shape}, {B.shape}, {C.shape}")
+    if b_is_a_t and m != n:
+        raise ValueError(f"SolveSylvester: B = A^T needs square operands of one size, got m = {m}, n = {n}")
+    bshape = tuple(np.broadcast_shapes(A.shape[:-2], B.shape[:-2], C.shape[:-2]))
+    nb = int(np.prod(bshape)) if bshape else 1
+    out = DeviceArray.empty((*bshape, m, n), out_dtype or A.dtype)
+    if nb == 0 or m * n == 0:
+        return out
+    if max(m, n) > MAX_SYLVESTER_SCHUR:
+        raise _sylvester_refused(m, n)
+    f64 = "float64"
+    Ab = _batchify(A, 2, bshape)
+    Bb = None if b_is_a_t else _batchify(B, 2, bshape)
+    Cb = _batchify(C, 2, bshape)
+    if str(Cb.dtype) != f64:
+        Cb = _cast(env, Cb, f64)
+    ws_bytes = int(env.lib.pthip_sylvester_workspace(nb, m, n, int(b_is_a_t)))
+    ws = DeviceArray.empty(((ws_bytes + 7) // 8,), f64)
+    env.timed(f"real_schur_{A.dtype}_{m}x{n}_b{nb}", lambda: ffi.check(env.lib.pthip_real_schur(
+        _dt(Ab), nb, m, n, int(b_is_a_t), Ab.ptr, None if Bb is None else Bb.ptr, ws.ptr, ws_bytes)))
+    # the orthogonal factors, stored transposed (csrc/schur_device.h): U(i, j) = Zt[j, i]; workspace layout in pthip.h
+    U = ws.view((nb, m, m), (2 * m * m, 1, m), m * m)
+    V = U if b_is_a_t else ws.view((nb, n, n), (2 * n * n, 1, n), 2 * nb * m * m + n * n)
+    tr = lambda x: x.view(x.shape, (x.strides[0], x.strides[2], x.strides[1]), 0)
+    F = gemm_device(env, 1.0, gemm_device(env, 1.0, tr(U), Cb, batch=True), V, batch=True)  # U^T C V
+    env.timed(f"trsyl_{m}x{n}_b{nb}", lambda: ffi.check(env.lib.pthip_trsyl(nb, m, n, int(b_is_a_t), F.ptr, ws.ptr, ws_bytes)))
+    X = gemm_device(env, 1.0, gemm_device(env, 1.0, U, F, batch=True), tr(V), batch=True)  # U Y V^T
+    env.keepalive.extend((ws, F, Ab, Cb) + (() if Bb is None else (Bb,)))
+    if np.dtype(out.dtype) != np.dtype(f64):
+        X = _cast(env, X, out.dtype)
+    return X.view(out.shape, contiguous_strides(out.shape))
 
 
 @handler("SolveSylvester")
 def solve_sylvester(node, inputs, env):
     """``A X + X B = C`` (linalg/solvers/linear_control.py:117 ``SolveSylvester``; the reference builds
-    it from real Schur forms and LAPACK ``trsyl``).  Here the equation is solved as the linear system it
-    is: (A (x) I_n + I_m (x) B^T) vec(X) = vec(C) with row-major vec, assembled by one generated kernel
-    and handed to the LU solver — O((m n)^3), for the m n <= 4096 of state-space models; the unique
-    solution whenever the spectra of A and -B are disjoint, like Bartels-Stewart's."""
+    it from real Schur forms and LAPACK ``trsyl``).  Two tiers (DESIGN §4 "Sylvester / Lyapunov"):
+
+    - m n <= 4096: the linear system it is, (A (x) I_n + I_m (x) B^T) vec(X) = vec(C) with row-major vec,
+      assembled by one generated kernel and handed to the LU solver — O((m n)^3);
+    - m, n <= 1024 above that: Bartels-Stewart (``solve_sylvester_schur``), O(m^3 + n^3), with one Schur form
+      when B = A^T (the ``b_is_a_t`` param of the lowering).
+
+    Both give the unique solution whenever the spectra of A and -B are disjoint."""
     from pytensor_amd.dispatch.lu import solve_general
+    from pytensor_amd.dispatch.riccati import out_dtype
 
     A, B, Cm = _same_float(env, inputs, "SolveSylvester")
     m, n = A.shape[0], B.shape[0]
@@ -450,8 +518,11 @@ def solve_sylvester(node, inputs, env):
         raise ValueError(f"SolveSylvester: incompatible shapes {A.shape}, {B.shape}, {Cm.shape}")
     if m * n == 0:
         return [DeviceArray.empty((m, n), A.dtype)]
-    if m * n > MAX_SYLVESTER:
-        raise NotImplementedError(f"hip linker: SolveSylvester with m*n = {m * n} (Kronecker tier, up to {MAX_SYLVESTER})")
+    tier = sylvester_tier(m, n)
+    if tier is None:
+        raise _sylvester_refused(m, n)
+    if tier == "schur":
+        return [solve_sylvester_schur(env, A, B, Cm, bool(node.params.get("b_is_a_t", False)), out_dtype(env, node))]
     dt = str(A.dtype)
     eye = lambda k: env.to_device(HostValue(np.eye(k, dtype=A.dtype)))
     Im, In = eye(m), eye(n)

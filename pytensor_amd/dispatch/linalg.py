@@ -193,6 +193,11 @@ def blockwise(node, inputs, env):
         from pytensor_amd.dispatch import riccati
 
         return [riccati.dare_device(env, *ins, riccati.out_dtype(env, node))]
+    if p["core_op"] == "SolveSylvester" and len(ins) == 3:  # (above the Kronecker bound: one batched call)
+        from pytensor_amd.dispatch import decomp, riccati
+
+        if decomp.sylvester_tier(ins[0].shape[-1], ins[1].shape[-1]) == "schur":
+            return [decomp.solve_sylvester_schur(env, *ins, bool(cp.get("b_is_a_t", False)), riccati.out_dtype(env, node))]
     return _blockwise_loop(node, ins, env, inputs)
 
 

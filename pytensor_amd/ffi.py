@@ -157,6 +157,9 @@ SIGNATURES = {
     "pthip_dare": (_int, [_int, _int, _i64, _i64, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _sz]),
     "pthip_dare_guard": (_int, [_i64, _vp, _vp, _int]),
     "pthip_dare_finish": (_int, [_int, _i64, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "pthip_sylvester_workspace": (_sz, [_i64, _i64, _i64, _int]),
+    "pthip_real_schur": (_int, [_int, _i64, _i64, _i64, _int, _vp, _vp, _vp, _sz]),
+    "pthip_trsyl": (_int, [_i64, _i64, _i64, _int, _vp, _vp, _sz]),
     "pthip_logsumexp_cols": (_int, [_int, _i64, _i64, _i64, _vp, _vp, _vp, _sz]),
     "pthip_softmax_cols": (_int, [_int, _int, _i64, _i64, _i64, _vp, _vp, _vp, _sz]),
     "pthip_cumulative": (_int, [_int, _int, _i64, _i64, _i64, _vp, _vp]),

@@ -515,6 +515,8 @@ def _(op, node, ctx):
     if core is None or core[0] in ("Blockwise", "HostPerform"):
         return None
     name, params = core
+    if name == "SolveSylvester":  # (the dummy core node has fresh inputs: look at the batched ones)
+        params = {**params, "b_is_a_t": sylvester_b_is_a_t(node)}
     if core is _INLINE:
         # the core op is an OpFromGraph without a kernel of its own (AllocDiag in the Cholesky pullback,
         # ...): its inner graph, lowered once, is what the host loop runs per batch item
@@ -729,14 +731,35 @@ def _register_ifelse():
 _register_ifelse()
 
 
+def sylvester_b_is_a_t(node) -> bool:
+    """Whether the operands (A, B, C) of a SolveSylvester (or its Blockwise) node have B = A^T: one of A, B is a
+    DimShuffle of the other that swaps the last two axes and keeps the leading ones (solve_continuous_lyapunov passes
+    (A, A^T); the bilinear solve_discrete_lyapunov, after the rewrites, (B^T, B))."""
+    from pytensor.tensor.elemwise import DimShuffle
+
+    if node is None or len(node.inputs) != 3:
+        return False
+
+    def is_t(x, y):
+        o = x.owner
+        if o is None or not isinstance(o.op, DimShuffle) or o.inputs[0] is not y:
+            return False
+        nd = y.type.ndim
+        return nd >= 2 and tuple(o.op.new_order) == (*range(nd - 2), nd - 1, nd - 2)
+
+    a, b = node.inputs[0], node.inputs[1]
+    return is_t(a, b) or is_t(b, a)
+
+
 def _register_ofg():
     from pytensor.compile.builders import OpFromGraph
     from pytensor.tensor.linalg.solvers.linear_control import SolveDiscreteARE, SolveSylvester
 
     @hip_funcify.register(SolveSylvester)
     def _(op, node, ctx):
-        # (its inner graph is Schur + TRSYL, which have no lowering: the equation is solved directly)
-        return "SolveSylvester", {}
+        # (its inner graph is Schur + TRSYL, which have no lowering: the equation is solved directly.  b_is_a_t: the
+        #  Lyapunov case B = A^T, which the Bartels-Stewart tier solves with one Schur form, dispatch/decomp.py)
+        return "SolveSylvester", {"b_is_a_t": sylvester_b_is_a_t(node)}
 
     @hip_funcify.register(SolveDiscreteARE)
     def _(op, node, ctx):
