@@ -6,7 +6,14 @@ Cholesky(128)), fp64.  Data (y, X, gidx, Sigma) are shared variables resident in
 the timed region starts; the parameters (small) go in and the 6 outputs come out through
 the boundary on every step (both inside the timed region).
 
-    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR]
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
+
+A plain run does what the headline figure needs and nothing else: it sets up (data, the compiled plan, the
+``Function``), checks once that the plan reproduces the eager outputs bit for bit (the 64 untimed replays that also bring
+clocks and caches to steady state), warms up, times the K steps, writes the outputs if asked and prints the result line.
+Every other measurement and check described below (``value_executor_level``, ``roofline``, ``cpu_baseline`` and its parity
+gate, ``configs``, ``mfma_util``, ``--hotpath``) runs only under ``--full``; without it those fields are absent or null and no
+detail file is written unless ``--detail`` names one.
 
 ``--dump-outputs DIR`` (e.g. the git-ignored ``bench_outputs/``) writes the six outputs of the last timed step (rank 0) as ``DIR/<name>.npy`` in fp64
 (``C4_OUTPUT_NAMES``); the inputs are seeded, so two builds run with the same arguments can be compared output for output.
@@ -20,10 +27,10 @@ SURVEY.md §8e) and ``value`` = total evals / max-over-ranks time.
 ``value`` / ``ms_per_step`` time the drop-in API: ``pytensor.function(params, outs, mode="hip")`` ->
 ``Function.__call__`` with ``trust_input=True``, on every rank (needs the importable reference copy ``oracle/_ref``,
 which travels with the snapshot; without it the executor-level loop is timed and ``config.value_is`` says so).
-``value_executor_level`` / ``ms_per_step_executor_level`` time the same K steps on the compiled ``HipExecutable``
+``value_executor_level`` / ``ms_per_step_executor_level`` (``--full``) time the same K steps on the compiled ``HipExecutable``
 plan called directly — the object ``HipLinker.jit_compile`` returns.
 
-The JSON line also carries
+Under ``--full`` the JSON line also carries
   roofline      the dominant kernel (gchain_*: one pass over X for X@beta and X.T@w): algorithmic
                 bytes (N*K*8 + 2*N*8 per launch) / mean launch duration measured live with HIP
                 events on the context stream; ``traffic`` = HBM bytes per launch from two
@@ -248,6 +255,10 @@ def parse_args(argv=None):
     ap.add_argument("--steps", type=int, default=200)
     ap.add_argument("--warmup", type=int, default=20)
     ap.add_argument("--rows", dest="n", type=int, default=1_000_000, help="observations N")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also run every secondary measurement and check: the executor-level loop, the roofline of the "
+                         "dominant kernel with its counter passes, the CPU baseline and its parity gate, the other BASELINE configs "
+                         "(the --no-* options below and --hotpath select among these)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-via-function", action="store_true", help="time the executor-level loop instead of pytensor.function(mode='hip')")
     ap.add_argument("--no-settle", action="store_true", help="no untimed settle evaluations before --warmup (see warmup_effective)")
@@ -255,13 +266,14 @@ def parse_args(argv=None):
     ap.add_argument("--no-live-pmc", action="store_true", help="roofline.traffic from the committed PMC summary instead of two rocprofv3 --pmc passes inside this run")
     ap.add_argument("--eager", action="store_true", help="per-node dispatch instead of the frozen hipGraph plan")
     ap.add_argument("--single-stream", action="store_true", help="frozen plan without the two-stream fork")
-    ap.add_argument("--hotpath", action="store_true", help="also run the 45-case hot_* sweep (cold + warm), the blocked Cholesky and the GP graph (minutes; detail file only)")
+    ap.add_argument("--hotpath", action="store_true", help="also run the 45-case hot_* sweep (cold + warm), the blocked Cholesky and the GP graph (minutes; detail file only; implies --full)")
     ap.add_argument("--detail", default=None, help="where the full record goes (default: gpurun_out/bench_detail.json when gpurun_out/ exists, else bench_detail.json)")
     ap.add_argument("--dump-outputs", metavar="DIR", default=None,
                     help="write the outputs of the last timed step (rank 0) as DIR/<name>.npy, fp64, for output-for-output comparison of two builds")
     args = ap.parse_args(argv)
     if args.steps < 1:
         ap.error("--steps must be >= 1")
+    args.full = args.full or args.hotpath
     return args
 
 
@@ -290,7 +302,7 @@ def dump_outputs(outs, names, out_dir):
 
 
 def measure(args):
-    """Runs the timed region and every secondary measurement; returns the FULL record (rank 0) or None (other ranks).
+    """Runs the timed region and, under ``--full``, every secondary measurement; returns the FULL record (rank 0) or None (other ranks).
     ``main`` prints only ``compact(record)`` as the final stdout line; the full record goes to the detail file."""
     from pytensor_amd import replicas
 
@@ -352,6 +364,40 @@ def measure(args):
         exe_f = f.vm.jit_fn
         fn_stats = {"compile_s": t_compile, "replays": exe_f.stats["replays"], "eager_calls": exe_f.stats["eager_calls"],
                     "resident_uploads": exe_f.stats["resident_uploads"], "resident_mode": resident_mode}
+
+    line = {
+        "metric": "graph evals/sec (logp+grad, N=1e6 fp64)",
+        "value": args.steps * info.world / elapsed,
+        "unit": "graph evals/sec",
+        "n_gpus": info.world,
+        "steps": args.steps,
+        "warmup": args.warmup,
+        # evaluations actually run before the timed region: 1 eager + 1 plan check + the 64-replay determinism gate
+        # + --warmup (the gate is what brings clocks / caches / the interpreter to steady state before K = 20 steps)
+        "warmup_effective": args.warmup + n_settle + (4 if fn is not None else 0),
+        "untimed_gate_evals_executor_level": 64 + (2 if plan is not None else 1),
+        "ms_per_step": elapsed / args.steps * 1e3,
+        "higher_is_better": True,
+        "scaling": "weak",
+        "vs_baseline": None,
+        "dtype": "f64",
+        "data": "synthetic",
+        "full": args.full,
+        "config": {
+            "workload": "BASELINE.json configs[3]: hierarchical-normal logp + grad, N=%d, K=128, G=128, Cholesky(128); one chain per GPU" % args.n,
+            "mode": "eager" if args.eager else "hipGraph plan",
+            # `value` = K evaluations through pytensor.function(mode="hip") -> Function.__call__ (trust_input=True): the drop-in
+            # API (every rank times its own Function; when oracle/_ref is absent the executor-level loop is timed instead).
+            # value_executor_level (--full): the same K steps on the compiled plan called directly.
+            "value_is": ("pytensor.function(params, outs, mode='hip') called K times (Function.__call__, trust_input=True); value_executor_level = the compiled plan called directly"
+                         if fn is not None else "executor-level loop (oracle/_ref absent or --no-via-function: no pytensor.function on this box)"),
+            "function": fn_stats,
+            "parallelism": f"replicas x{info.world}",
+        },
+    }
+    if not args.full:
+        # a plain run ends here: the headline figure needs nothing of what follows
+        return line if info.rank == 0 else None
 
     # ---- secondary: the same K steps on the executor-level loop (the compiled plan called directly, no Function) ----
     for _ in range(args.warmup):
@@ -433,36 +479,9 @@ def measure(args):
         mfma = {"dot22_f64_4096": d[0] if d else None, "bdot_f32_512x256": round(sum(b) / len(b), 4) if b else None,
                 "source": "profiles/r7_mfma_pmc.json (rocprofv3 --pmc SQ_VALU_MFMA_BUSY_CYCLES, committed)"}
 
-    line = {
-        "metric": "graph evals/sec (logp+grad, N=1e6 fp64)",
-        "value": args.steps * info.world / elapsed,
-        "unit": "graph evals/sec",
-        "n_gpus": info.world,
-        "steps": args.steps,
-        "warmup": args.warmup,
-        # evaluations actually run before the timed region: 1 eager + 1 plan check + the 64-replay determinism gate
-        # + --warmup (the gate is what brings clocks / caches / the interpreter to steady state before K = 20 steps)
-        "warmup_effective": args.warmup + n_settle + (4 if fn is not None else 0),
-        "untimed_gate_evals_executor_level": 64 + (2 if plan is not None else 1),
-        "ms_per_step": elapsed / args.steps * 1e3,
-        # `value` = K evaluations through pytensor.function(mode="hip") -> Function.__call__ (trust_input=True): the drop-in
-        # API (every rank times its own Function; when oracle/_ref is absent the executor-level loop is timed instead and
-        # config.value_is says so).  value_executor_level: the same K steps on the compiled plan called directly.
+    line.update({
         "value_executor_level": args.steps / elapsed_exec,
         "ms_per_step_executor_level": elapsed_exec / args.steps * 1e3,
-        "higher_is_better": True,
-        "scaling": "weak",
-        "vs_baseline": None,
-        "dtype": "f64",
-        "data": "synthetic",
-        "config": {
-            "workload": "BASELINE.json configs[3]: hierarchical-normal logp + grad, N=%d, K=128, G=128, Cholesky(128); one chain per GPU" % args.n,
-            "mode": "eager" if args.eager else "hipGraph plan",
-            "value_is": ("pytensor.function(params, outs, mode='hip') called K times (Function.__call__, trust_input=True); value_executor_level = the compiled plan called directly"
-                         if fn is not None else "executor-level loop (oracle/_ref absent or --no-via-function: no pytensor.function on this box)"),
-            "function": fn_stats,
-            "parallelism": f"replicas x{info.world}",
-        },
         "roofline": {
             "bound": "hbm",
             "kernel": kernel_name,
@@ -484,7 +503,7 @@ def measure(args):
         "cpu_baseline": cpu,
         "configs": cfgs,
         "mfma_util": mfma,
-    }
+    })
     return line
 
 
@@ -510,11 +529,13 @@ def compact(full, detail_path=None):
         out[k] = _r(out[k], 6)
     cfg = full.get("config") or {}
     out["config"] = {"workload": _short(cfg.get("workload"), 160), "parallelism": cfg.get("parallelism"), "api": _short(cfg.get("value_is"), 90)}
-    rf = full.get("roofline") or {}
-    out["roofline"] = {k: _r(rf.get(k)) for k in ("bound", "achieved", "peak", "unit", "frac", "traffic")}
-    out["roofline"]["kernel"] = _short(rf.get("kernel"), 70)
-    out["roofline"]["kernel_ms"] = _r((rf.get("detail") or {}).get("kernel_ms"), 6)
-    out["roofline"]["traffic_source"] = _short(rf.get("traffic_source"), 60)
+    rf = full.get("roofline")
+    out["roofline"] = None  # a plain run (no --full) measures none
+    if rf:
+        out["roofline"] = {k: _r(rf.get(k)) for k in ("bound", "achieved", "peak", "unit", "frac", "traffic")}
+        out["roofline"]["kernel"] = _short(rf.get("kernel"), 70)
+        out["roofline"]["kernel_ms"] = _r((rf.get("detail") or {}).get("kernel_ms"), 6)
+        out["roofline"]["traffic_source"] = _short(rf.get("traffic_source"), 60)
     cpu = full.get("cpu_baseline")
     if cpu:
         out["cpu_baseline"] = {k: _r(cpu.get(k)) for k in ("value", "unit", "cores", "kind", "ms_per_eval", "parity_err_over_bound")}
@@ -536,7 +557,9 @@ def compact(full, detail_path=None):
     out["configs"] = fr
     if full.get("mfma_util"):
         out["mfma_util"] = {k: v for k, v in full["mfma_util"].items() if k != "source"}
-    out["value_executor_level"] = _r(full.get("value_executor_level"), 2)
+    if full.get("value_executor_level") is not None:
+        out["value_executor_level"] = _r(full["value_executor_level"], 2)
+    out["full"] = bool(full.get("full"))
     if detail_path:
         out["detail"] = detail_path
     text = json.dumps(out)
@@ -553,6 +576,9 @@ def main(argv=None):
     args = parse_args(argv)
     full = measure(args)
     if full is None:
+        return
+    if not args.full and args.detail is None:
+        print(json.dumps(compact(full)), flush=True)  # a plain run: the one line, no side file
         return
     detail = args.detail
     if detail is None:

@@ -91,6 +91,49 @@ def test_default_run_skips_the_sweep():
     assert args.steps * 0.2e-3 < 60  # default K at ~0.2 ms per evaluation: seconds, not minutes
 
 
+def lean_record():
+    """what ``measure`` returns for a plain run: the headline fields, none of the ``--full`` measurements"""
+    rec = fat_record(0)
+    for k in ("value_executor_level", "roofline", "cpu_baseline", "configs"):
+        del rec[k]
+    rec["full"] = False
+    return rec
+
+
+def test_full_is_an_option_and_off_by_default():
+    assert bench.parse_args([]).full is False
+    assert bench.parse_args(["--gpus", "1", "--steps", "3", "--warmup", "1"]).full is False
+    assert bench.parse_args(["--full"]).full is True
+    assert bench.parse_args(["--hotpath"]).full is True  # the sweep is one of the measurements --full runs
+
+
+def test_plain_run_prints_the_headline_and_writes_no_side_file(monkeypatch, capsys, tmp_path):
+    monkeypatch.setattr(bench, "measure", lambda args: lean_record())
+    monkeypatch.setattr(bench, "ROOT", str(tmp_path))  # where a detail file would go by default
+    bench.main(["--gpus", "1", "--steps", "20", "--warmup", "5"])
+    lines = [ln for ln in capsys.readouterr().out.splitlines() if ln.strip()]
+    assert len(lines) == 1
+    rec = json.loads(lines[0])
+    assert rec["metric"] == "graph evals/sec (logp+grad, N=1e6 fp64)" and rec["unit"] == "graph evals/sec"
+    assert rec["value"] == 5234.123457 and rec["ms_per_step"] == 0.191235 and rec["higher_is_better"] is True and rec["dtype"] == "f64"
+    assert rec["full"] is False and rec["roofline"] is None and rec["cpu_baseline"] is None and rec["configs"] == {}
+    assert "value_executor_level" not in rec and "detail" not in rec
+    assert not list(tmp_path.iterdir())
+    # the same record with --detail: the side file is written where asked
+    bench.main(["--detail", str(tmp_path / "d.json")])
+    assert json.load(open(tmp_path / "d.json"))["full"] is False
+
+
+def test_plain_run_returns_before_any_secondary_measurement():
+    """``measure`` leaves through the ``not args.full`` return before the first line of the secondary section"""
+    src = open(os.path.join(ROOT, "bench.py")).read()
+    body = src[src.index("def measure(args):"):src.index("MAX_LINE =")]
+    leave = body.index("if not args.full:")
+    for later in ("elapsed_exec", "exe.profile_nodes(", "live_pmc_traffic(", "pmc_c4_current.json", "cpu_baseline(graph", "bench_configs.measure(", "r7_mfma_pmc.json"):
+        assert body.index(later) > leave, later
+    assert body.index("dump_outputs(last") < leave and body.index('"ms_per_step"') < leave
+
+
 def test_dump_outputs_writes_one_npy_per_output(tmp_path):
     import numpy as np
 

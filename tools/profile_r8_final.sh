@@ -8,7 +8,7 @@ O=$R/gpurun_out/$TAG
 mkdir -p $O
 export TMPDIR=/tmp
 cd /tmp
-python $R/bench.py --steps 300 --warmup 30 > $O/bench.json 2> $O/bench.err
+python $R/bench.py --full --steps 300 --warmup 30 > $O/bench.json 2> $O/bench.err
 cp $R/gpurun_out/bench_detail.json $O/bench_detail.json 2>/dev/null
 rocprofv3 --kernel-trace --stats -d /tmp/pk_$TAG -o k -- python $R/bench.py --steps 200 --warmup 20 --no-cpu-baseline --no-configs --no-live-pmc > $O/bench_under_rocprof.json 2> $O/kt.err
 python $R/tools/rocpd_stats.py $(find /tmp/pk_$TAG -name "*.db" | head -1) > $O/c4_kernel_stats.md
