@@ -376,6 +376,21 @@ int pthip_permuted_identity(int dtype, int64_t n, const void* perm, void* out);
 int pthip_trsm(int dtype, int lower, int trans, int unit_diag, int64_t batch, int64_t n,
                int64_t nrhs, const void* T, int64_t sTb, int64_t sT0, int64_t sT1, const void* B,
                int64_t sBb, void* out);
+/* Batched general solve in one launch (LAPACK gesv = getrf + getrs behind Blockwise(Solve), solvers/general.py
+ * Solve.perform, and behind Blockwise(MatrixInverse), linalg/inverse.py:87), n <= 64: X[b] (n x nrhs, contiguous)
+ * = A[b]^-1 B[b].  A[b] is read at A + b*sAb + i*sA0 + j*sA1 (elements; sAb = 0: one matrix for the whole batch,
+ * factored once per wavefront), B[b] (n x nrhs row-major) at B + b*sBb (0: one right-hand side block for all).
+ * B == NULL: the identity, i.e. the inverse (pass nrhs = n).  An exactly zero or NaN pivot NaN-fills the item's X
+ * and leaves its neighbours alone; with flag_singular a zero pivot also raises bit 1 (value 2) of the device error
+ * word, like pthip_getrf. */
+int pthip_gesv_batched(int dtype, int64_t batch, int64_t n, int64_t nrhs, const void* A, int64_t sAb,
+                       int64_t sA0, int64_t sA1, const void* B, int64_t sBb, void* X, int flag_singular);
+/* out[b] (n x nrhs, contiguous) = P[b] * B[b] for the gather vectors perm (int64, n each, at perm + b*sPb; sPb = 0:
+ * one factorisation shared by the batch) of pthip_getrf: row i of out[b] is row perm[b][i] of B[b] (n x nrhs
+ * row-major at B + b*sBb).  B == NULL: of the identity (the right-hand side of a batched inverse above the
+ * one-launch tier). */
+int pthip_laswp_batched(int dtype, int64_t batch, int64_t n, int64_t nrhs, const void* B, int64_t sBb,
+                        const void* perm, int64_t sPb, void* out);
 
 /* ---- indexing / data movement (bit-exact tier; pytensor/tensor/subtensor.py:868-2614,
  *      pytensor/tensor/basic.py:1545 Alloc, 2405 Join, compile/ops.py:121 DeepCopyOp) ---- */

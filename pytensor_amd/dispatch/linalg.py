@@ -177,6 +177,10 @@ def blockwise(node, inputs, env):
             return [lu._solve(env, cp, ins[0], ins[1])]
         fake = type("_N", (), {"params": cp})
         return (lu.det if p["core_op"] == "Det" else lu.slogdet)(fake, ins, env)
+    if p["core_op"] == "MatrixInverse":  # (one launch for the whole stack up to n = 64: lu.solve_tier)
+        from pytensor_amd.dispatch import lu
+
+        return lu.matrix_inverse(type("_N", (), {"params": cp}), ins, env)
     if p["core_op"] == "LUFactor":
         from pytensor_amd.dispatch import lu
 
@@ -185,7 +189,7 @@ def blockwise(node, inputs, env):
         from pytensor_amd.dispatch import lu
 
         return lu.pivot_to_permutations(type("_N", (), {"params": cp}), ins, env)
-    if p["core_op"] == "Eigh" and len(ins) == 1:  # (the generalised problem loops its items below)
+    if p["core_op"] == "Eigh":  # (standard or generalised: every kernel either is composed of takes the batch)
         from pytensor_amd.dispatch import lu
 
         return lu.eigh(type("_N", (), {"params": cp}), ins, env)

@@ -52,30 +52,128 @@ def _permute_rows(env, b: DeviceArray, perm: DeviceArray) -> DeviceArray:
     return out
 
 
-def solve_general(env, A: DeviceArray, b: DeviceArray, b_ndim: int) -> DeviceArray:
-    """x = A^-1 b through P A = L U: permute b, unit-lower solve, upper solve.  A singular U has a
-    zero pivot, which the triangular solve turns into the reference's NaN fill."""
+WAVE_MAX_N = 64  # csrc/lu_batched.hip: one lane per row, the row in registers
+
+
+def solve_tier(n: int, nb: int) -> str:
+    """How a general solve / inverse of ``nb`` systems of order ``n`` runs:
+
+    ``"wave"``      n <= 64, any ``nb`` (the unbatched solve of a Scan step included): one launch of
+                    ``pthip_gesv_batched`` factors, permutes and substitutes for the whole batch.
+    ``"composed"``  n > 64, two items or more: ``pthip_getrf`` with ``batch = nb``, one batched row gather
+                    (``pthip_laswp_batched``) and two batched ``pthip_trsm`` — four calls whatever ``nb`` is.  Up
+                    to the one-workgroup LDS bound of getrf (n <= ~140 fp64 / ~200 fp32) those are four launches;
+                    beyond it ``getrf_typed`` walks the matrices inside the call (the blocked factorisation keeps
+                    the whole device busy with one matrix), and that stays.
+    ``"loop"``      n > 64 and at most one item: nothing to batch, the per-item sequence."""
+    if n <= WAVE_MAX_N:
+        return "wave"
+    return "composed" if nb >= 2 else "loop"
+
+
+def _batch_strides(x: DeviceArray, core_ndim: int, bshape):
+    """Element strides of ``x``'s leading dims broadcast to ``bshape`` (0 along a broadcast dim)."""
+    lead = x.shape[: x.ndim - core_ndim]
+    pad = len(bshape) - len(lead)
+    return (0,) * pad + tuple(0 if s == 1 else st for s, st in zip(lead, x.strides[: len(lead)]))
+
+
+def _collapse_batch(bshape, *stride_sets):
+    """Fold the batch dims, innermost first, into one count with ONE stride per operand — what a kernel that takes
+    a batch stride can walk by itself.  Returns (outer, inner, strides): ``outer`` lists the (size, stride per
+    operand) of the leading dims that do not fold (the caller loops them), ``inner`` the folded count."""
+    dims = [(s, [ss[d] for ss in stride_sets]) for d, s in enumerate(bshape) if s != 1]
+    inner, st = 1, [0] * len(stride_sets)
+    while dims:
+        s, sts = dims[-1]
+        if inner > 1 and any(a != b * inner for a, b in zip(sts, st)):
+            break
+        if inner == 1:
+            st = list(sts)
+        inner *= s
+        dims.pop()
+    return dims, inner, st
+
+
+def _gesv_wave(env, A: DeviceArray, b, b_ndim: int, out: DeviceArray, bshape, flag_singular: bool):
+    """``out`` (contiguous, (*bshape, *core)) = A^-1 b (``b`` None: the inverse) through pthip_gesv_batched.
+    Broadcast and strided batch dims go to the kernel as strides; dims that do not fold into one stride (``A``
+    (5,1,n,n) against ``b`` (1,7,n,k)) are walked here, one launch per outer index, and nothing is copied."""
     n = A.shape[-1]
+    nrhs = n if b is None else (1 if b_ndim == 1 else b.shape[-1])
+    sets = [_batch_strides(A, 2, bshape)]
+    if b is not None:
+        core_b = b.shape[b.ndim - b_ndim :]
+        # (the stride of a core dim of length 1 is never read: it forces no copy)
+        if any(s != 1 and st != c for s, st, c in zip(core_b, b.strides[b.ndim - b_ndim :], contiguous_strides(core_b))):
+            b = b.contiguous()
+        sets.append(_batch_strides(b, b_ndim, bshape))
+    outer, inner, st = _collapse_batch(bshape, *sets)
+    isz, per = A.itemsize, n * nrhs
+    for f, idx in enumerate(np.ndindex(*[s for s, _ in outer])):
+        offs = [sum(i * sts[k] for i, (_, sts) in zip(idx, outer)) for k in range(len(sets))]
+        ffi.check(env.lib.pthip_gesv_batched(
+            _dt(A), inner, n, nrhs, A.ptr + offs[0] * isz, st[0], A.strides[-2], A.strides[-1],
+            None if b is None else b.ptr + offs[1] * isz, 0 if b is None else st[1], out.ptr + f * inner * per * isz,
+            int(flag_singular)))
+
+
+def _solve_composed(env, A: DeviceArray, b, b_ndim: int, out: DeviceArray, bshape, flag_singular: bool):
+    """The composed tier: batched getrf, one batched row gather, two batched triangular solves.  A matrix shared
+    by the whole batch is factored once and handed on with a batch stride of 0."""
+    n = A.shape[-1]
+    nb = int(np.prod(bshape))
+    nrhs = n if b is None else (1 if b_ndim == 1 else b.shape[-1])
+    shared = int(np.prod(A.shape[:-2])) == 1
+    LU, perm, _, _, _ = getrf_device(env, A.view((n, n), A.strides[-2:]) if shared else _batchify(A, 2, bshape).view((nb, n, n), (n * n, n, 1)),
+                                     flag_singular=flag_singular)
+    sTb = 0 if shared else n * n
+    bptr, sBb = None, 0
+    if b is not None:
+        if int(np.prod(b.shape[: b.ndim - b_ndim])) == 1:
+            bm = b.contiguous()
+        else:
+            bm, sBb = _batchify(b, b_ndim, bshape), n * nrhs
+        bptr = bm.ptr
+    pb = DeviceArray.empty((nb, n, nrhs), A.dtype)
+    y = DeviceArray.empty((nb, n, nrhs), A.dtype)
+    ffi.check(env.lib.pthip_laswp_batched(_dt(A), nb, n, nrhs, bptr, sBb, perm.ptr, 0 if shared else n, pb.ptr))
+    ffi.check(env.lib.pthip_trsm(_dt(A), 1, 0, 1, nb, n, nrhs, LU.ptr, sTb, n, 1, pb.ptr, n * nrhs, y.ptr))
+    ffi.check(env.lib.pthip_trsm(_dt(A), 0, 0, 0, nb, n, nrhs, LU.ptr, sTb, n, 1, y.ptr, n * nrhs, out.ptr))
+
+
+def solve_general(env, A: DeviceArray, b: DeviceArray, b_ndim: int) -> DeviceArray:
+    """x = A^-1 b through P A = L U, by the tier ``solve_tier`` names.  A singular U has a zero pivot, which every
+    tier turns into the reference's NaN fill of that item."""
+    n = A.shape[-1]
+    if A.shape[-2] != n:
+        raise ValueError("Solve: expected a square matrix")
     if b.shape[b.ndim - b_ndim] != n:
         raise ValueError(f"Solve: incompatible shapes {A.shape} and {b.shape}")
     if str(b.dtype) != str(A.dtype):
         raise TypeError("Solve: dtype mismatch")
+    bA, bb = A.shape[:-2], b.shape[: b.ndim - b_ndim]
+    bshape = tuple(np.broadcast_shapes(bA, bb))
+    core_b = b.shape[b.ndim - b_ndim :]
+    nb = int(np.prod(bshape)) if bshape else 1
+    tier = solve_tier(n, nb)
+    if tier != "loop":
+        out = DeviceArray.empty((*bshape, *core_b), b.dtype)
+        if out.size:
+            (_gesv_wave if tier == "wave" else _solve_composed)(env, A, b, b_ndim, out, bshape, False)
+        return out
     if A.ndim == 2 and b.ndim == b_ndim:
         LU, perm, _, _, _ = getrf_device(env, A)
         lu = LU.view((n, n), (n, 1))
         pb = _permute_rows(env, b, perm.view((n,), (1,)))
         y = trsm_device(env, lu, pb, True, True, b_ndim)
         return trsm_device(env, lu, y, False, False, b_ndim)
-    # batched: loop the (small) batch on the host — each item is three launches
-    bA, bb = A.shape[:-2], b.shape[: b.ndim - b_ndim]
-    bshape = tuple(np.broadcast_shapes(bA, bb))
-    core_b = b.shape[b.ndim - b_ndim :]
+    # (at most one item behind leading dims of length 1 — or none at all)
     Ab = _batchify(A, 2, bshape)
     bbm = _batchify(b, b_ndim, bshape)
     out = DeviceArray.empty((*bshape, *core_b), b.dtype)
-    nb = Ab.shape[0]
     step = int(np.prod(core_b)) if core_b else 1
-    for k in range(nb):
+    for k in range(Ab.shape[0]):
         Ak = Ab.view((n, n), (n, 1), k * n * n)
         bk = bbm.view(core_b, contiguous_strides(core_b), k * step)
         xk = solve_general(env, Ak, bk, b_ndim)
@@ -176,17 +274,28 @@ def slogdet(node, inputs, env):
 
 @handler("MatrixInverse")
 def matrix_inverse(node, inputs, env):
+    """``np.linalg.inv`` of a (..., n, n) stack (LinAlgError when an item is singular), by the tiers of
+    ``solve_tier`` with the identity as the right-hand side (generated on the device)."""
     x = env.to_device(inputs[0])
     n = x.shape[-1]
-    if x.ndim != 2:
-        raise NotImplementedError("hip linker: batched MatrixInverse")
-    LU, perm, _, _, _ = getrf_device(env, x, flag_singular=True)  # np.linalg.inv raises when singular
+    if x.ndim < 2 or x.shape[-2] != n:
+        raise ValueError("MatrixInverse: expected square matrices")
+    bshape = x.shape[:-2]
+    nb = int(np.prod(bshape)) if bshape else 1
+    tier = solve_tier(n, nb)
+    if tier != "loop":
+        out = DeviceArray.empty(x.shape, x.dtype)
+        if out.size:
+            (_gesv_wave if tier == "wave" else _solve_composed)(env, x, None, 2, out, bshape, True)
+        return [out]
+    if nb == 0:
+        return [DeviceArray.empty(x.shape, x.dtype)]
+    LU, perm, _, _, _ = getrf_device(env, x.view((n, n), x.strides[-2:]), flag_singular=True)  # np.linalg.inv raises when singular
     lu = LU.view((n, n), (n, 1))
     pb = DeviceArray.empty((n, n), x.dtype)  # P * I, built on the device (no upload per call)
-    if n:
-        ffi.check(env.lib.pthip_permuted_identity(_dt(x), n, perm.ptr, pb.ptr))
+    ffi.check(env.lib.pthip_permuted_identity(_dt(x), n, perm.ptr, pb.ptr))
     y = trsm_device(env, lu, pb, True, True, 2)
-    return [trsm_device(env, lu, y, False, False, 2)]
+    return [trsm_device(env, lu, y, False, False, 2).view(x.shape, contiguous_strides(x.shape))]
 
 
 @handler("Eigh")
@@ -227,21 +336,20 @@ def _eigh_generalised(node, inputs, env):
     """``A v = w B v`` (Eigh with two inputs; perform = ``scipy.linalg.eigh(a, b, lower=)``, LAPACK
     sygvd): the same reduction LAPACK's ``sygst`` does, out of kernels that exist — ``B = L L^T``
     (potrf), ``C = L^-1 A L^-T`` (two multi-rhs triangular solves), the standard problem for C
-    (Jacobi), ``v = L^-T y``.  Eigenvectors come out B-orthonormal (``v^T B v = I``) like scipy's."""
+    (Jacobi), ``v = L^-T y``.  Eigenvectors come out B-orthonormal (``v^T B v = I``) like scipy's.  Every one of
+    those kernels takes a batch, so leading dims are a batch here too (``Blockwise``)."""
     from pytensor_amd.dispatch.linalg import _lapack_operands
 
     a, b = _lapack_operands(env, "Eigh", *inputs)
     n = a.shape[-1]
     if a.shape[-2] != n or b.shape[-2:] != (n, n):
         raise ValueError(f"Eigh: incompatible shapes {a.shape} and {b.shape}")
-    if a.ndim != 2 or b.ndim != 2:
-        raise NotImplementedError("hip linker: batched generalised Eigh")
     lower = bool(node.params["lower"])
     A = _symmetrize(env, a, lower)
     B = _symmetrize(env, b, lower)
     L = cholesky_device(env, B, True)
-    Y = trsm_device(env, L, A, True, False, 2)  # L Y = A
-    Yt = Y.view((n, n), (Y.strides[1], Y.strides[0])).contiguous()
+    Y = trsm_device(env, L, A, True, False, 2)  # L Y = A  (leading dims: a batch, broadcast by the solve)
+    Yt = Y.view(Y.shape, (*Y.strides[:-2], Y.strides[-1], Y.strides[-2])).contiguous()
     Cm = trsm_device(env, L, Yt, True, False, 2)  # L C = Y^T  ->  C = L^-1 A L^-T (symmetric)
     fake = type("_N", (), {"params": {"lower": True}})
     w, y = eigh(fake, [Cm], env)

@@ -143,6 +143,8 @@ SIGNATURES = {
     "pthip_gttrs": (_int, [_int, _i64, _i64, _i64, _int, _vp, _vp, _vp, _vp, _vp, _vp]),
     "pthip_random_multinomial": (_int, [_int, _i64, _i64, _vp, _vp, _vp, _int, _i64, _vp, _i64, _vp]),
     "pthip_trsm": (_int, [_int, _int, _int, _int, _i64, _i64, _i64, _vp, _i64, _i64, _i64, _vp, _i64, _vp]),
+    "pthip_gesv_batched": (_int, [_int, _i64, _i64, _i64, _vp, _i64, _i64, _i64, _vp, _i64, _vp, _int]),
+    "pthip_laswp_batched": (_int, [_int, _i64, _i64, _i64, _vp, _i64, _vp, _i64, _vp]),
     "pthip_copy_strided": (_int, [_int, _int, C.POINTER(_i64), _vp, C.POINTER(_i64), _vp, C.POINTER(_i64)]),
     "pthip_take_rows": (_int, [_int, _i64, _i64, _vp, _i64, _i64, _vp, _vp]),
     "pthip_scatter_rows_workspace": (_sz, [_i64, _i64, _i64]),
