@@ -107,7 +107,7 @@ def r6_refsuite_fixes():
 
 @case("r6_device_math", rtol=1.2e-15)
 def r6_device_math():
-    """The generated kernels' own fp64 log / log1p (codegen.PRELUDE pt_log / pt_log1p, round 6) and what calls them (softplus,
+    """The generated kernels' own fp64 log / log1p (csrc/scalar_device.h pt_log / pt_log1p, round 6) and what calls them (softplus,
     the shared sigmoid / softplus pair, log1mexp) against the reference's libm values, at a tolerance of ~5 ulp: arguments of
     every magnitude and both signs, the neighbourhoods of the reduction's switch points, subnormals."""
     rng = np.random.default_rng(612)

@@ -7,7 +7,8 @@ Layout (only what the hot path needs):
 * ``ir.py``      portable lowered-graph IR
 * ``lower.py``   PyTensor ``FunctionGraph`` → IR (needs PyTensor)
 * ``linker.py``  ``HipLinker(JITLinker)`` + mode/linker registration (needs PyTensor)
-* ``codegen.py`` ``Composite`` scalar graph → fused HIP kernel source
+* ``codegen_scalar.py`` ``Composite`` scalar graph → device statements (helpers: ``csrc/scalar_device.h``, ``csrc/special_*.h``)
+* ``codegen*.py``  the generated kernels around them: flat / N-d (``codegen.py``), tiled, ``gchain``, ``dotew``, tail
 * ``executor.py``/``dispatch/``  runs the IR on the device
 """
 

@@ -31,17 +31,14 @@ from __future__ import annotations
 
 from pytensor_amd.codegen import (
     BLOCK,
-    CTYPE,
     PT_PAIR_HELPERS,
     REDUCE_OPS,
     VEC_HELPERS,
     _reduce_epilogue,
     _stream_load,
     _vec_type,
-    emit_body,
-    prelude_for,
-    reduce_header,
 )
+from pytensor_amd.codegen_scalar import CTYPE, device_header, emit_body, prelude_for
 
 MAX_BATCH = 3  # outer dimensions beyond the tile's row dimension (MAX_ND = 5 collapsed dims)
 
@@ -76,7 +73,7 @@ def tile_kernel_source(name: str, body: dict, cls: str, nb: int, V: int, TX: int
     if "T" in cls:
         assert lds_rows == TR
     P = tile_params(body, cls, nb, reduce_spec)
-    L = [reduce_header() if any(reduce_spec) else "", prelude_for(body), VEC_HELPERS]
+    L = [device_header("reduce_device.h") if any(reduce_spec) else "", prelude_for(body), VEC_HELPERS]
     L.append(f'extern "C" __global__ __launch_bounds__({BLOCK}) void {name}({", ".join(P)}) {{')
     L.append(f"  constexpr int TX = {TX}, TY = {TY}, RPT = {RPT}, V = {V}, TC = {TC}, TR = {TR};")
     # ---- workgroup-uniform decomposition of the tile index ----
@@ -362,7 +359,7 @@ def tile_reduce_source(name: str, body: dict, cls: str, nkb: int, nrd: int, row_
     P = tile_reduce_params(body, cls, nkb, nrd, outs, finish)
     if finish:
         assert not any(op == "LogSumExp" for op, _, _ in outs)
-    L = [reduce_header(), prelude_for(body), VEC_HELPERS, PT_PAIR_HELPERS if finish else ""]
+    L = [device_header("reduce_device.h"), prelude_for(body), VEC_HELPERS, PT_PAIR_HELPERS if finish else ""]
     L.append(f'extern "C" __global__ __launch_bounds__({BLOCK}) void {name}({", ".join(P)}) {{')
     L.append(f"  constexpr int TX = {TX}, TY = {TY}, RPT = {RPT}, V = {V}, TC = {TC}, TR = {TR};")
     L.append("  unsigned pt_t = blockIdx.x;")

@@ -1,4 +1,4 @@
-// exp_device.h — the 24-instruction fp64 exp of the generated kernels (pytensor_amd/codegen.py PRELUDE: pt_exp /
+// exp_device.h — the 24-instruction fp64 exp of the generated kernels (pytensor_amd/csrc/scalar_device.h: pt_exp /
 // pt_exp_k, where its derivation and accuracy figures are: <= 1 ulp on 6e5 points in [-700, 700]) for the hand-written
 // kernels of csrc/softmax.hip.  The device library's exp is ~34 instructions and, in unrolled code with many
 // instances, every polynomial coefficient is materialised again per instance (two v_mov_b32 of a literal per Horner

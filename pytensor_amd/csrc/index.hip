@@ -53,7 +53,7 @@ __global__ __launch_bounds__(BLOCK) void fill_kernel(T* __restrict__ dst, const 
 }
 
 // B (K x N, any strides) -> the MFMA-operand order of the generated skinny-product kernels
-// (codegen.dot_epilogue_source): Bp[N/16][K/4][16][4], Bp[ct][k4][j][q] = B[4*k4 + q][16*ct + j],
+// (codegen_dotew.dot_epilogue_source): Bp[N/16][K/4][16][4], Bp[ct][k4][j][q] = B[4*k4 + q][16*ct + j],
 // zero-padded to multiples of 16 in both extents.  One thread per destination element: writes
 // fully coalesced, reads 16-element row segments (a once-per-evaluation repack of a loop constant).
 template <typename T>

@@ -6,7 +6,7 @@
 // pytensor/tensor/elemwise.py:1233).  Each is a few microseconds of work behind ~4.5 us of
 // dependent-launch latency.  `pthip_multi_finish` takes up to 16 slabs of different shapes and
 // reduces each from [nparts, M] to [S, M] (S <= 16 row chunks) in ONE launch; the generated tail
-// kernel (codegen.tail_chain_source) adds the S rows in order while it applies the epilogues and
+// kernel (codegen_tail.tail_chain_source) adds the S rows in order while it applies the epilogues and
 // the scalar graph behind them.  Blocks map to (task, column tile, row chunk) through a prefix
 // table; a tile is 16 adjacent columns (128-byte row segments), 16 row lanes walk their chunk with
 // 4 independent accumulators (the slab is latency-bound: 2 MB must be in flight at once, hence
@@ -39,7 +39,7 @@ __global__ void join_signal_kernel(int* word) { __hip_atomic_store(word, 1, __AT
 __global__ __launch_bounds__(256) void join_probe_write_kernel(unsigned* __restrict__ buf, int n, unsigned val) {
   for (int i = blockIdx.x * 256 + threadIdx.x; i < n; i += gridDim.x * 256) buf[i] = val ^ (unsigned)i;
 }
-// the consumer side exactly as the generated tail kernel has it (codegen._tail_prologue): a relaxed agent-scope spin
+// the consumer side exactly as the generated tail kernel has it (codegen_tail._tail_prologue): a relaxed agent-scope spin
 // on the word, NO fence behind it, plain loads of what the other stream wrote
 __global__ __launch_bounds__(256) void join_probe_wait_kernel(int* word, const unsigned* __restrict__ buf, int n, unsigned val,
                                                              int* bad) {

@@ -3,7 +3,7 @@
 Produced by ``gemmfuse.fuse_dot_epilogue`` inside ``Scan`` steps: ``out = body(.., A_d @ W_d, ..)``
 with ``W_d`` loop constants.  Reference ops restated: ``Dot22``/``Gemm`` (pytensor/tensor/blas/
 gemm.py:76,248 — the alpha/beta epilogue already lives in ``body``) followed by ``Elemwise``
-(pytensor/tensor/elemwise.py:755).  The generated kernel (codegen.dot_epilogue_source) covers
+(pytensor/tensor/elemwise.py:755).  The generated kernel (codegen_dotew.dot_epilogue_source) covers
 ``K % 16 == 0``, rows of A 16-byte aligned, M up to ``MAX_ROWS``; anything else runs the plain
 MFMA GEMM followed by the ordinary elementwise kernel — same values, two launches per product.
 """
@@ -13,7 +13,7 @@ from __future__ import annotations
 import os
 import struct
 
-from pytensor_amd import codegen, ffi, kernel_cache
+from pytensor_amd import codegen, codegen_dotew, ffi, kernel_cache
 from pytensor_amd.device import DeviceArray
 from pytensor_amd.dispatch import handler
 from pytensor_amd.dispatch.blas import _prep2d, gemm_device
@@ -92,7 +92,7 @@ def dot_epilogue(node, inputs, env):
     T = body["in_dtypes"][dpos[0]]
     K = dots[dpos[0]][0].shape[1]
     fast = (
-        M > 0 and N > 0 and 0 < K <= codegen.DOTEW_MAX_K and K % 16 == 0 and M <= MAX_ROWS
+        M > 0 and N > 0 and 0 < K <= codegen_dotew.DOTEW_MAX_K and K % 16 == 0 and M <= MAX_ROWS
         and T in ("float32", "float64") and all(body["in_dtypes"][q] == T for q in dpos)
     )
     for q in dpos:
@@ -113,7 +113,7 @@ def dot_epilogue(node, inputs, env):
     # register buffers of 8 k-groups (two in flight = every load of a K=1024 product): 16.0 us per
     # GRU step; 16 (both products of the update gate in flight, ~300 VGPRs) measured 17.4
     # (profiles/r2f_c5_chunk.txt)
-    chunk = int(os.environ.get("PTHIP_DOTEW_CHUNK", 0)) or codegen.DOTEW_CHUNK
+    chunk = int(os.environ.get("PTHIP_DOTEW_CHUNK", 0)) or codegen_dotew.DOTEW_CHUNK
     name = f"dotew_{_body_key(body)}_k{K}_d{'_'.join(map(str, dpos))}_u{chunk}" + ("_c" + "_".join(map(str, sorted(byvalue))) if byvalue else "")
     # products with the very same left operand stream it once
     share = {}
@@ -150,7 +150,7 @@ def dot_epilogue(node, inputs, env):
     var = os.environ.get("PTHIP_DOTEW_VAR", "acc4")  # accumulator chains; other values: tools/dotew_variants.py timing-only decompositions
     if var:
         name += "_" + var.replace(",", "_")
-    src = codegen.dot_epilogue_source(name, body, dpos, K, byvalue, chunk, share, lds_a, var, set(packed_a), pack_outs)
+    src = codegen_dotew.dot_epilogue_source(name, body, dpos, K, byvalue, chunk, share, lds_a, var, set(packed_a), pack_outs)
     fn = kernel_cache.get_function(src, name)
     args = [M, N]
     for k, a in enumerate(ins):

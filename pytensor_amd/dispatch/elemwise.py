@@ -15,7 +15,7 @@ import struct
 
 import numpy as np
 
-from pytensor_amd import codegen, ffi, kernel_cache
+from pytensor_amd import codegen, codegen_scalar, ffi, kernel_cache
 from pytensor_amd.device import DeviceArray
 from pytensor_amd.dispatch import handler
 from pytensor_amd.executor import HOST_MAX, HostValue
@@ -760,7 +760,7 @@ def tiled_copy(dst: DeviceArray, src: DeviceArray) -> bool:
     """``dst[...] = src`` (same shape, ``dst`` contiguous, ``src`` any strides, 0 on broadcast dimensions) through
     the tiled N-d loop.  False when the dtype or the shape is outside what it covers."""
     dt = str(dst.dtype)
-    if dt not in codegen.CTYPE or not _TILE:
+    if dt not in codegen_scalar.CTYPE or not _TILE:
         return False
     shape = tuple(dst.shape)
     cshape, cstr = _collapse(shape, [tuple(src.strides), _cstrides(shape)])

@@ -17,7 +17,7 @@ import struct
 
 import numpy as np
 
-from pytensor_amd import codegen, ffi, kernel_cache
+from pytensor_amd import codegen_gchain, ffi, kernel_cache
 from pytensor_amd.device import DeviceArray, copy_into
 from pytensor_amd.dispatch import handler
 from pytensor_amd.dispatch.blas import _scalar, gemv_device
@@ -29,7 +29,7 @@ CHAIN_RG = int(os.environ.get("PTHIP_CHAIN_RG", 0))  # 0 = auto
 # on C4 (evals/s): 448: 3252, 480: 3220, 512: 3209, 1024: 3274, 2048: 3331, 4096: 3282 —
 # a persistent grid that leaves CUs free for the overlapped latency chain does not pay.
 CHAIN_GRID = int(os.environ.get("PTHIP_CHAIN_GRID", 2048))
-MAX_SCATTER_BINS = 256  # 64 bins per accumulator register of a lane, up to four (codegen.gemv_chain_source)
+MAX_SCATTER_BINS = 256  # 64 bins per accumulator register of a lane, up to four (codegen_gchain.gemv_chain_source)
 MAX_CHAIN_K = 4096  # columns the one-pass kernel holds in registers (32 chunks of 128: one row per group)
 
 
@@ -162,7 +162,7 @@ def gemv_chain(node, inputs, env):
     if scatter_out is not None:
         sgroups = max(1, (base.shape[0] + 63) // 64)
         name += f"_b{sgroups}"
-    src = codegen.gemv_chain_source(name, body, e_modes, rs, w_out, C, RG, store_r, y1d is not None, out_store, scatter_out, sgroups, pack, atype)
+    src = codegen_gchain.gemv_chain_source(name, body, e_modes, rs, w_out, C, RG, store_r, y1d is not None, out_store, scatter_out, sgroups, pack, atype)
     fn = kernel_cache.get_function(src, name)
     ngroups = (N + RG - 1) // RG
     grid = max(1, min((ngroups + 3) // 4, CHAIN_GRID))

@@ -34,7 +34,7 @@ def _inner_executable(node, env) -> HipExecutable:
 
 def _pack_plan(ig, info):
     """Which step-kernel outputs are multiplied FROM THE LEFT by a later step kernel (``DotEpilogue``)
-    and should therefore also be stored in the MFMA operand order (codegen.dot_epilogue_source
+    and should therefore also be stored in the MFMA operand order (codegen_dotew.dot_epilogue_source
     ``pack_outs`` / ``packed_a``): values consumed inside the same step, and recurrent states whose
     tap of a later step feeds such a product (a sit-sot / mit-sot tap -k of step t IS the state's
     output of step t-k, scan/op.py:322-635).  Returns (inner output/temporary var ids to pack,

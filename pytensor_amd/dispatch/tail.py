@@ -5,7 +5,7 @@ pytensor/tensor/blas/gemv.py:64-108, ``Elemwise`` / ``ElemwiseReduce`` = elemwis
 1233, ``DimShuffle`` = a view, elemwise.py:41); this handler only decides *how many launches*
 they cost.  Extents are checked at run time: when every operand is a scalar or a short vector,
 ``pthip_multi_finish`` shrinks the large partial slabs and ONE generated single-workgroup kernel
-does the rest (``codegen.tail_chain_source``); otherwise the members run through their own
+does the rest (``codegen_tail.tail_chain_source``); otherwise the members run through their own
 handlers, exactly as before the fusion.
 """
 
@@ -17,7 +17,7 @@ import struct
 
 import numpy as np
 
-from pytensor_amd import codegen, ffi, kernel_cache
+from pytensor_amd import codegen, codegen_scalar, codegen_tail, ffi, kernel_cache
 from pytensor_amd.device import DeviceArray
 from pytensor_amd.dispatch import HANDLERS, handler
 from pytensor_amd.dispatch.elemwise import _body_key, _scalar_bits
@@ -73,7 +73,7 @@ class _Planner:
             if v.a.size != 1:
                 raise _Infeasible("host array operand")
             dt = str(v.a.dtype)
-            if dt not in codegen.CTYPE:
+            if dt not in codegen_scalar.CTYPE:
                 raise _Infeasible(dt)
             self.ext.append({"kind": "C", "dtype": dt})
             self.ext_len.append(1)
@@ -84,7 +84,7 @@ class _Planner:
         if not isinstance(v, DeviceArray):
             raise _Infeasible(type(v).__name__)
         dt = str(v.dtype)
-        if dt not in codegen.CTYPE:
+        if dt not in codegen_scalar.CTYPE:
             raise _Infeasible(dt)
         n = _vec_len(v.shape)
         if n is None or n > MAX_LEN:
@@ -124,7 +124,7 @@ class _Planner:
         d = val.dev
         if not isinstance(d, DeferredReduce):
             raise _Infeasible("large operand")
-        if d.spec["op"] not in codegen.REDUCE_OPS or d.spec["acc_dtype"] not in codegen.CTYPE:
+        if d.spec["op"] not in codegen.REDUCE_OPS or d.spec["acc_dtype"] not in codegen_scalar.CTYPE:
             raise _Infeasible("reduction op")
         out = self.new_slot((), d.spec["dtype"])
         src = self.add_slab(d.parts)
@@ -215,7 +215,7 @@ def _plan(node, inputs, env):
                 if n is None or n > MAX_LEN or len(base.shape) != 1:
                     raise _Infeasible("scatter base")
             ys = [P.materialise(vals[v]) for v in sub.inputs[1:]]
-            if any(y.size != 1 for y in ys) or base.dtype not in codegen.CTYPE:
+            if any(y.size != 1 for y in ys) or base.dtype not in codegen_scalar.CTYPE:
                 raise _Infeasible("scatter operand")
             idx = []
             for k in sub.params["indices"]:
@@ -230,7 +230,7 @@ def _plan(node, inputs, env):
             vals[sub.outputs[0]] = out
         else:  # Elemwise / ElemwiseReduce
             body = sub.params["scalar"]
-            if not codegen.supported(body):
+            if not codegen_scalar.supported(body):
                 raise _Infeasible("scalar op")
             ins = [P.materialise(vals[v]) for v in sub.inputs]
             nd = max((len(v.shape) for v in ins), default=0)
@@ -285,12 +285,12 @@ _FUSE_SHRINK = os.environ.get("PTHIP_TAIL_FUSE_SHRINK", "0") == "1"
 def _run_fused(node, P, results, env, inputs=()):
     lib = env.lib
     # launch 1: every large slab -> <= 16 rows.  When the slabs fit ONE task table of one dtype, that work
-    # becomes the prologue of the chain's own launch instead (last-workgroup ticket, codegen._tail_prologue)
+    # becomes the prologue of the chain's own launch instead (last-workgroup ticket, codegen_tail._tail_prologue)
     by_dt = {}
     for t in P.shrink:
         by_dt.setdefault(str(t[1].dtype), []).append(t)
     fuse_shrink = None
-    if _FUSE_SHRINK and len(by_dt) == 1 and 1 <= len(P.shrink) <= codegen.TAIL_SHRINK_MAX_TASKS:
+    if _FUSE_SHRINK and len(by_dt) == 1 and 1 <= len(P.shrink) <= codegen_tail.TAIL_SHRINK_MAX_TASKS:
         fuse_shrink = {"dtype": next(iter(by_dt))}
     # the plan's device-side join (plan.py _DEV_JOIN; include/pthip.h pthip_join_signal): the chain launch waits for the
     # other stream's signal word and puts it back
@@ -334,7 +334,7 @@ def _run_fused(node, P, results, env, inputs=()):
                 [{k: (_body_key(v) if k == "body" else v) for k, v in st.items()} for st in P.steps], spec["outs"]])
     # short operands (the usual case: K- and G-vectors, <= 16-row slabs): the form that requests
     # every global operand before the first step; size classes are part of the kernel identity
-    sizes = codegen.tail_preload_sizes(spec, P.ext_len, P.step_n) if os.environ.get("PTHIP_TAIL_PRELOAD", "1") != "0" else None
+    sizes = codegen_tail.tail_preload_sizes(spec, P.ext_len, P.step_n) if os.environ.get("PTHIP_TAIL_PRELOAD", "1") != "0" else None
     args = [a for e in P.ext_args for a in e] + [("q", o) for o in offs] + [a for s in P.step_args for a in s] + out_args
     status = getattr(env, "tail_status", None) or (0, 0, 0)
     join = join_ptr
@@ -358,7 +358,7 @@ def _run_fused(node, P, results, env, inputs=()):
                     (C.c_void_p * n)(*[t[5].ptr for t in chunk])))
     grid = 1
     if fuse_shrink is not None:
-        tasks, grid = codegen.tail_shrink_pack([(t[0], t[1].ptr, t[2], t[3], t[4], t[5].ptr) for t in P.shrink])
+        tasks, grid = codegen_tail.tail_shrink_pack([(t[0], t[1].ptr, t[2], t[3], t[4], t[5].ptr) for t in P.shrink])
         if len(buf) + len(tasks) + 8 > 4000:
             # the task table does not fit the 4 KB argument block next to the chain's own arguments: two launches
             fuse_shrink = None
@@ -373,13 +373,13 @@ def _run_fused(node, P, results, env, inputs=()):
             ffi.check(lib.pthip_ticket_slot(C.byref(slot)))
             buf += tasks + struct.pack("<Q", slot.value)
     name = "tail_" + codegen.source_key(key + repr(sizes) + repr(fuse_shrink))[:16]
-    src = codegen.tail_chain_source(name, spec, sizes, shrink=fuse_shrink)
+    src = codegen_tail.tail_chain_source(name, spec, sizes, shrink=fuse_shrink)
     fn = kernel_cache.get_function(src, name)
     if len(buf) > 4000:
         raise _Infeasible("kernel argument block")  # (4 KB kernarg limit: run the members instead)
     kt = env.kernel_timer
     tok = kt.begin() if kt is not None else None
-    ffi.check(lib.pthip_launch(fn, grid, 1, 1, codegen.TAIL_BLOCK, 1, 1, max(off, 16), buf, len(buf)))
+    ffi.check(lib.pthip_launch(fn, grid, 1, 1, codegen_tail.TAIL_BLOCK, 1, 1, max(off, 16), buf, len(buf)))
     if kt is not None:
         kt.end(name, tok)
     if status[1]:

@@ -13,7 +13,7 @@ from __future__ import annotations
 import ctypes as C
 import struct
 
-from pytensor_amd import codegen, ffi, kernel_cache
+from pytensor_amd import codegen, codegen_scalar, ffi, kernel_cache
 from pytensor_amd.device import DeviceArray
 from pytensor_amd.dispatch import HANDLERS, handler
 from pytensor_amd.dispatch.elemwise import (
@@ -48,11 +48,11 @@ def _term_cost(body, modes=None) -> float:
     """Estimated VALU instructions per ELEMENT.  Scalar ops none of whose operands vary with the element (``exp(-log_sigma)``
     of a broadcast parameter) are hoisted out of the loop by the compiler and cost nothing; ``sigmoid`` and ``softplus`` of
     one operand share their exp and a division, divisions by one denominator share a reciprocal when every output is
-    summed (codegen.emit_body) — the estimate has to rank the families the way the generated code costs them, or the
+    summed (codegen_scalar.emit_body) — the estimate has to rank the families the way the generated code costs them, or the
     cheap families finish early and the launch ends on a few workgroups of the dear one."""
     nodes = body["body"]
     if modes is None or any(n["op"] in ("ScalarLoop", "LoopOut") for n in nodes):
-        return 8.0 + sum(_OP_COST.get(op, 1.5) for op in codegen.body_ops(body))
+        return 8.0 + sum(_OP_COST.get(op, 1.5) for op in codegen_scalar.body_ops(body))
     varies = []
     cost = 8.0
     seen_den, seen_sig = set(), {}
@@ -134,7 +134,7 @@ def multi_elemwise(node, inputs, env):
         ins = [_scalar_or_device(env, i) for i in inputs[pos : pos + t["n_inputs"]]]
         pos += t["n_inputs"]
         ft = _flat_term(t, ins)
-        if ft is None or not codegen.supported(t["scalar"]):
+        if ft is None or not codegen_scalar.supported(t["scalar"]):
             return _run_members(node, inputs, env)
         per_term.append((t, ins, *ft))
     nt = len(per_term)

@@ -236,7 +236,7 @@ def fuse_dot_epilogue(g: Graph) -> Graph:
     right operand is a loop constant (a non-sequence of the Scan) it is repacked once per
     evaluation (``PackB16``, hoisted into the outer graph like ``merge_sibling_gemms`` hoists
     its ``Join``) and the product, its slab sum and the consuming ``Composite`` become one
-    generated kernel (codegen.dot_epilogue_source): a GRU step is two dependent launches.
+    generated kernel (codegen_dotew.dot_epilogue_source): a GRU step is two dependent launches.
     Several products feeding one ``Elemwise`` (``rh@U_h`` and ``h@U_z`` of the update gate) are
     accumulated in the same launch.  Shapes the kernel does not cover are decided at run time
     by the handler (dispatch/blas.py: plain GEMM + elementwise kernel).
@@ -334,7 +334,7 @@ def _dot_epilogue_in_scan(g: Graph, scan: Node, new_vars: dict):
 def _hoist_shared_left_operand(inner: Graph, nodes, ivars):
     """``h @ U_z`` of a later ``DotEpilogue`` moves into the earlier one that already streams ``h``
     (``h @ U_r``): the generated kernel loads the shared left operand once and runs two accumulator
-    chains (codegen.dot_epilogue_source ``share``); the moved product leaves as an extra raw output
+    chains (codegen_dotew.dot_epilogue_source ``share``); the moved product leaves as an extra raw output
     and enters its old consumer as an ordinary elementwise operand.  Per GRU step: 64 KB less per
     workgroup, and the second launch — the longer one — loses a whole product.
 

@@ -222,12 +222,12 @@ def _(op, node, ctx):
 
 def _require_device_body(body, op):
     """fail at compile time, not at the first call: every scalar op and dtype of the fused body
-    must have a device expression (codegen.SCALAR_EXPR)"""
-    from pytensor_amd import codegen
+    must have a device expression (codegen_scalar.SCALAR_EXPR)"""
+    from pytensor_amd import codegen_scalar
 
-    if not codegen.supported(body):
-        missing = sorted({o for o in codegen.body_ops(body) if o not in codegen.SCALAR_EXPR})
-        dts = sorted({d for d in body["in_dtypes"] + body["out_dtypes"] if d not in codegen.CTYPE})
+    if not codegen_scalar.supported(body):
+        missing = sorted({o for o in codegen_scalar.body_ops(body) if o not in codegen_scalar.SCALAR_EXPR})
+        dts = sorted({d for d in body["in_dtypes"] + body["out_dtypes"] if d not in codegen_scalar.CTYPE})
         what = ", ".join([*(f"scalar op {m}" for m in missing), *(f"dtype {d}" for d in dts)]) or "an inner loop dtype"
         raise NotImplementedError(f"hip linker: no device code for {what} (in {op})")
 

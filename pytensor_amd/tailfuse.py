@@ -10,7 +10,7 @@ the fix is structural: every node at the end of the graph whose operands are sma
 ``Tail`` node, executed as
 
 * ``pthip_multi_finish`` (csrc/tail.hip): all large partial slabs shrunk to ≤16 rows, one launch;
-* one generated single-workgroup kernel (``codegen.tail_chain_source``): sums those rows and
+* one generated single-workgroup kernel (``codegen_tail.tail_chain_source``): sums those rows and
   the deferred per-workgroup partials of earlier reductions, applies the Gemv epilogues and runs
   the small ``Elemwise`` / ``ElemwiseReduce`` nodes in order with intermediates in LDS, then
   writes the results — inside a frozen plan straight into the pinned output block.

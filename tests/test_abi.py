@@ -54,27 +54,27 @@ def test_product_path_fails_loudly_without_gpu():
 def test_optional_special_function_helpers_compile_without_gpu():
     """the long scalar helpers (incomplete gamma / beta and their inverses, polygamma) are emitted only
     into kernels that use them: each combination must pass hiprtc on its own"""
-    from pytensor_amd import codegen, ffi
+    from pytensor_amd import codegen_scalar, ffi
 
     for op, nin in (("NdtriExp", 1), ("PolyGamma", 2), ("GammaIncInv", 2), ("GammaIncCInv", 2), ("BetaIncInv", 3), ("GammaInc", 2), ("BetaInc", 3)):
         body = {"in_dtypes": ["float64"] * nin, "out_dtypes": ["float64"],
                 "body": [{"op": op, "in": [["i", k] for k in range(nin)], "dtype": "float64"}], "outs": [["t", 0]]}
         names = [f"v{k}" for k in range(nin)]
-        src = (codegen.prelude_for(body) + '\nextern "C" __global__ void probe(const double* a, double* o) {\n'
+        src = (codegen_scalar.prelude_for(body) + '\nextern "C" __global__ void probe(const double* a, double* o) {\n'
                + "".join(f"  const double {nm} = a[{k}];\n" for k, nm in enumerate(names)) + "  double r;\n"
-               + codegen.emit_body(body, names, ["r"], indent="  ") + "\n  o[0] = r;\n}\n")
+               + codegen_scalar.emit_body(body, names, ["r"], indent="  ") + "\n  o[0] = r;\n}\n")
         assert len(ffi.jit_compile(src, f"probe_{op}.hip")) > 1000, op
 
 
 def test_generated_tail_kernel_with_the_device_join_compiles_without_gpu():
     """both forms of the generated tail kernel carry the plan's device-side join in their prologue (wait for the other
     stream's signal word, put it back; a wait given up is reported through the done word as 2) and pass hiprtc"""
-    from pytensor_amd import codegen, ffi
+    from pytensor_amd import codegen_tail, ffi
 
     spec = {"ext": [{"kind": "P", "dtype": "float64"}], "slots": [{"dtype": "float64", "scalar": True}],
             "steps": [{"op": "rsum", "src": ("e", 0), "red": "Add", "acc_dtype": "float64", "dtype": "float64", "out": 0}], "outs": [0]}
-    plain = codegen.tail_chain_source("tail_probe", spec)
-    preload = codegen.tail_chain_source("tail_probe_p", spec, codegen.tail_preload_sizes(spec, [64], [64]))
+    plain = codegen_tail.tail_chain_source("tail_probe", spec)
+    preload = codegen_tail.tail_chain_source("tail_probe_p", spec, codegen_tail.tail_preload_sizes(spec, [64], [64]))
     for name, src in (("tail_probe", plain), ("tail_probe_p", preload)):
         assert "int* join_src" in src and "__hip_atomic_store(done_dst, 2," in src and "if (join_fail_) return;" in src
         # the wait sits in front of every operand request

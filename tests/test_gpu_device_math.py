@@ -1,4 +1,4 @@
-"""GPU: the generated kernels' own fp64 log1p and log (codegen.PRELUDE pt_log1p / pt_log: the classical 2^k (1 + f) reduction in
+"""GPU: the generated kernels' own fp64 log1p and log (csrc/scalar_device.h pt_log1p / pt_log: the classical 2^k (1 + f) reduction in
 ~60 / ~45 VALU instructions instead of the device library's ~125 / ~90) against long-double log1pl / logl, in ulps, over every magnitude and both
 signs, the k = 0 / k = 1 switch points, and the special values; softplus and the shared sigmoid / softplus pair that call it.
 The reference's Log1p / Softplus c_code is libm (scalar/basic.py:3042, scalar/math.py:1224): < 1 ulp — the bar here is 2.5 ulp

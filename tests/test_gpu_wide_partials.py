@@ -1,5 +1,5 @@
 """GPU: the tail kernel's wave-level fold of deferred reductions with MORE than 64 partials per reduction (two to four
-values per lane, added in index order, then the butterfly; codegen.TAIL_WAVE_Q).  The default many-term launch hands over
+values per lane, added in index order, then the butterfly; codegen_tail.TAIL_WAVE_Q).  The default many-term launch hands over
 at most 64 partials per term (dispatch/wide.TERM_CAP), so the wider fold is exercised here with the cap raised — in a
 subprocess, because the caps are read when the modules are imported."""
 import json

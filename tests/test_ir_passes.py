@@ -183,7 +183,7 @@ def test_inline_passes_units():
 def test_dot_epilogue_source_compiles_for_both_dtypes():
     """The generated product+epilogue kernel builds for gfx950 without a GPU (hiprtc), with the
     operand loads of both register buffers issued ahead of the first MFMA."""
-    from pytensor_amd import codegen, ffi
+    from pytensor_amd import codegen_dotew, ffi
 
     for dt, K in (("float32", 1024), ("float64", 48), ("float32", 16)):
         body = {
@@ -192,7 +192,7 @@ def test_dot_epilogue_source_compiles_for_both_dtypes():
                      {"op": "Mul", "in": [["t", 1], ["i", 2]], "dtype": dt}],
             "outs": [["t", 2]],
         }
-        src = codegen.dot_epilogue_source("dotew_probe", body, [1], K, byvalue=(2,))
+        src = codegen_dotew.dot_epilogue_source("dotew_probe", body, [1], K, byvalue=(2,))
         assert src.count("= __builtin_amdgcn_mfma") == (K // 16 + 3) // 4 * 4  # per wave: K/64 groups x 4
         assert len(ffi.jit_compile(src, "dotew_probe.hip")) > 1000
 
@@ -465,7 +465,7 @@ def test_identity_elemwise_behind_a_fused_logsumexp_is_dropped():
 
 
 def test_generated_scalar_code_shares_exp_and_reciprocals():
-    """round 6 (codegen.emit_body): sigmoid and softplus of ONE float64 operand -> one pt_sig_sp; divisions by one float64
+    """round 6 (codegen_scalar.emit_body): sigmoid and softplus of ONE float64 operand -> one pt_sig_sp; divisions by one float64
     denominator -> one reciprocal, but only where every output is summed (flat_kernel_source decides): an element-wise
     output keeps its exact quotient."""
     from pytensor_amd import codegen

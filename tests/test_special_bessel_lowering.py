@@ -40,12 +40,12 @@ def _graphs(pytensor, ptt):
 
 
 def _scalar_ops(f):
-    from pytensor_amd import codegen
+    from pytensor_amd import codegen_scalar
 
     g = f.maker.linker.last_ir
     ops = [n.op for n in g.nodes]
     assert "HostPerform" not in ops, ops
-    return {op for n in g.nodes if n.op == "Elemwise" for op in codegen.body_ops(n.params["scalar"])}
+    return {op for n in g.nodes if n.op == "Elemwise" for op in codegen_scalar.body_ops(n.params["scalar"])}
 
 
 @pytest.mark.parametrize("name", ["grad_i1", "ive", "iv", "log_iv", "kve", "kv", "kn", "jv", "owens_t", "grad_jv", "grad_log_kv", "grad_owens_t", "f32_jv"])
@@ -78,22 +78,22 @@ def test_hyp2f1_is_still_refused(pt):
 
 def test_kernel_source_carries_only_the_helpers_it_uses(pt):
     pytensor, ptt = pt
-    from pytensor_amd import codegen
+    from pytensor_amd import codegen_scalar
 
     x, v, h = ptt.dvector("x"), ptt.dvector("v"), ptt.dvector("h")
     f = pytensor.function([v, x, h], [ptt.jv(v, x), ptt.ive(v, x), ptt.kve(v, x), ptt.owens_t(h, x)], mode="hip")
     bodies = [n.params["scalar"] for n in f.maker.linker.last_ir.nodes if n.op == "Elemwise"]
-    assert {op for b in bodies for op in codegen.body_ops(b)} >= {"Jv", "Ive", "Kve", "Owens_t"}
-    full = codegen.prelude_for(*bodies)
+    assert {op for b in bodies for op in codegen_scalar.body_ops(b)} >= {"Jv", "Ive", "Kve", "Owens_t"}
+    full = codegen_scalar.prelude_for(*bodies)
     for fn in ("double pt_jv(", "double pt_ive(", "double pt_kve(", "double pt_owens_t("):
         assert fn in full
     plain = pytensor.function([x], ptt.exp(x) * ptt.i0(x), mode="hip")
-    src = codegen.prelude_for(*[n.params["scalar"] for n in plain.maker.linker.last_ir.nodes if n.op == "Elemwise"])
+    src = codegen_scalar.prelude_for(*[n.params["scalar"] for n in plain.maker.linker.last_ir.nodes if n.op == "Elemwise"])
     assert "pt_jv" not in src and "pt_owens_t" not in src and "pt_sf_" not in src
     # an Owen's T body does not carry the Bessel code, nor the reverse
-    ot = [b for b in bodies if "Owens_t" in set(codegen.body_ops(b))]
-    jv = [b for b in bodies if "Jv" in set(codegen.body_ops(b))]
-    assert "pt_jv" not in codegen.prelude_for(*ot) and "pt_owens_t" not in codegen.prelude_for(*jv)
+    ot = [b for b in bodies if "Owens_t" in set(codegen_scalar.body_ops(b))]
+    jv = [b for b in bodies if "Jv" in set(codegen_scalar.body_ops(b))]
+    assert "pt_jv" not in codegen_scalar.prelude_for(*ot) and "pt_owens_t" not in codegen_scalar.prelude_for(*jv)
 
 
 def test_flat_kernel_compiles_for_gfx950(pt):

@@ -61,12 +61,12 @@ def main():
     pytensor = E.activate()
     import pytensor.tensor as ptt
 
-    from pytensor_amd import codegen
+    from pytensor_amd import codegen_scalar
 
     rng = np.random.default_rng(0)
     for name, (ins, outs) in graphs(pytensor, ptt).items():
         f = pytensor.function(ins, outs, mode="hip")
-        ops = sorted({op for nd in f.maker.linker.last_ir.nodes if nd.op == "Elemwise" for op in codegen.body_ops(nd.params["scalar"])})
+        ops = sorted({op for nd in f.maker.linker.last_ir.nodes if nd.op == "Elemwise" for op in codegen_scalar.body_ops(nd.params["scalar"])})
         kinds = sorted({nd.op for nd in f.maker.linker.last_ir.nodes})
         c_s = None
         if not quick:
