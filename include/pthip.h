@@ -344,6 +344,11 @@ int pthip_convolve2d(int dtype, int64_t ha, int64_t wa, const void* a, int64_t h
  * row-major m x n matrices — Householder vectors below the diagonal (v_k = 1 implicit), R on and
  * above it with dlarfg's signs, tau[batch][min(m,n)] */
 int pthip_geqrf(int dtype, int64_t batch, int64_t m, int64_t n, void* A, void* tau);
+/* QR(pivoting=True).perform: LAPACK geqp3 (by its unblocked dlaqp2, every column) in place, A P = Q R left as
+ * pthip_geqrf leaves A = Q R; jpvt[batch][n] int32, 0-based: column j of A P is column jpvt[j] of A.  The pivot is the
+ * first position of the largest partial column norm; norms are downdated and recomputed by dlaqp2's rule.  The norm and
+ * permutation vectors live in LDS: an error above n = 5939 (fp64) / 9898 (fp32) columns */
+int pthip_geqp3(int dtype, int64_t batch, int64_t m, int64_t n, void* A, void* tau, void* jpvt);
 /* orgqr: Q (m x ncols, contiguous) = H_0 ... H_{k-1} applied to the leading columns of the identity;
  * QR as pthip_geqrf left it (row stride ldqr, qr_stride elements between batch items) */
 int pthip_orgqr(int dtype, int64_t batch, int64_t m, int64_t ncols, int64_t k, const void* QR, int64_t ldqr,

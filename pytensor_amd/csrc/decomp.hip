@@ -17,6 +17,8 @@
 //    of the null space / complement), which LAPACK does not fix either.
 #include "common.h"
 
+#include <limits>
+
 namespace {
 
 constexpr int BLOCK = 256;
@@ -152,6 +154,160 @@ __global__ __launch_bounds__(BLOCK) void geqrf_kernel(T* __restrict__ Aall, T* _
     __syncthreads();
     for (long long e = tid; e < (long long)m * n; e += BLOCK) Ag[e] = A[e];
   }
+}
+
+// ---- column-pivoted QR (dgeqp3 by its unblocked dlaqp2, every column) ---------------------------
+// (value, position) maximum: the larger value wins, the lower position among equal values; a total order, so
+// the result does not depend on the order in which pairs meet
+template <class T> __device__ __forceinline__ void argmax_take(T& v, int& p, T ov, int op) {
+  if (ov > v || (ov == v && op < p)) { v = ov; p = op; }
+}
+template <int CTRL, class T> __device__ __forceinline__ void argmax_dpp(T& v, int& p) {
+  const T ov = dpp_mov<CTRL>(v);
+  const int op = __builtin_amdgcn_update_dpp(0, p, CTRL, 0xf, 0xf, false);
+  argmax_take(v, p, ov, op);
+}
+// over the wave, in every lane: the DPP steps of wave_sum_dpp (the search sits on the critical path of every column)
+template <class T> __device__ __forceinline__ void wave_argmax(T& v, int& p) {
+  argmax_dpp<0xB1>(v, p);
+  argmax_dpp<0x4E>(v, p);
+  argmax_dpp<0x141>(v, p);
+  argmax_dpp<0x140>(v, p);  // every lane of a 16-lane row holds the row's pair
+  const T v0 = lane_bcast(v, 0);
+  const int p0 = __builtin_amdgcn_readlane(p, 0);
+  T bv = v0;
+  int bp = p0;
+  argmax_take(bv, bp, lane_bcast(v, 16), __builtin_amdgcn_readlane(p, 16));
+  argmax_take(bv, bp, lane_bcast(v, 32), __builtin_amdgcn_readlane(p, 32));
+  argmax_take(bv, bp, lane_bcast(v, 48), __builtin_amdgcn_readlane(p, 48));
+  v = bv; p = bp;
+}
+
+// vn1[c] = vn2[c] = ||M[r0:m, c]||_2 for the columns c0 <= c < c1 (all of them, or those whose vn2 holds the
+// marker -1): one row-contiguous pass, 64 columns x 4 row slices, the slices added in a fixed order.  s_w: 4 x 64
+template <class T>
+__device__ void column_norms(const T* __restrict__ M, long long ld, int r0, int m, int c0, int c1, bool marked_only,
+                             T* vn1, T* vn2, T* s_w) {
+  const int tid = threadIdx.x, tx = tid & 63, ty = tid >> 6;
+  for (int cc = c0; cc < c1; cc += 64) {
+    const int col = cc + tx;
+    const bool mine = col < c1 && (!marked_only || vn2[col] < T(0));
+    T acc = T(0);
+    if (mine) {
+#pragma unroll 8
+      for (int i = r0 + ty; i < m; i += 4) {
+        const T x = M[(long long)i * ld + col];
+        acc += x * x;
+      }
+    }
+    s_w[ty * 64 + tx] = acc;
+    __syncthreads();
+    if (mine && ty == 0) vn1[col] = vn2[col] = sqrt((s_w[tx] + s_w[64 + tx]) + (s_w[128 + tx] + s_w[192 + tx]));
+    __syncthreads();
+  }
+}
+
+// in place as geqrf_kernel leaves it (reflectors below the diagonal, R on and above it, tau[min(m,n)]) for A P, and
+// jpvt[n]: column j of A P is column jpvt[j] of A (0-based).  Dynamic LDS: [the matrix, if use_lds] vn1[n] vn2[n]
+// jpvt[n].  Per column k: the first position of the largest partial norm in k..n-1 (a NaN norm counts as -1: it
+// never wins), the swap, dlarfg + the update as in geqrf_kernel, then dlaqp2's downdating: vn1[j] *= sqrt(t),
+// t = max(0, 1 - (|A[k,j]| / vn1[j])^2), unless t (vn1[j]/vn2[j])^2 <= sqrt(eps), when the norm of A[k+1:m, j] is
+// recomputed (one shared pass for all such columns of the step).  The step is a chain of barriers, so the extra
+// work rides on barriers that are there anyway: the downdating of step k is done by the scan of step k+1's search
+// (each position belongs to one thread), the "recompute" vote by the barrier of the search's reduction, the swap
+// by the pass that sums the new column for dlarfg.  Every index comes from a loop counter: non-finite data give
+// meaningless numbers, and still a permutation.
+template <class T, int VM>
+__global__ __launch_bounds__(BLOCK) void geqp3_kernel(T* __restrict__ Aall, T* __restrict__ tauall, int* __restrict__ jpvtall,
+                                                     int m, int n, int use_lds) {
+  extern __shared__ __attribute__((aligned(16))) unsigned char qr_smem[];
+  __shared__ T s_v[VM];
+  __shared__ T s_w[256];
+  __shared__ T s_red[BLOCK / 64];
+  __shared__ int s_pos[BLOCK / 64];
+  T* Ag = Aall + (long long)blockIdx.x * m * n;
+  T* A = use_lds ? (T*)qr_smem : Ag;
+  T* vn1 = (T*)qr_smem + (use_lds ? (long long)m * n : 0);
+  T* vn2 = vn1 + n;
+  int* jp = (int*)(vn2 + n);
+  const int K = m < n ? m : n;
+  T* tau = tauall + (long long)blockIdx.x * K;
+  int* jpvt = jpvtall + (long long)blockIdx.x * n;
+  const int tid = threadIdx.x;
+  const T tol3z = sqrt(std::numeric_limits<T>::epsilon());
+  if (use_lds)
+    for (long long e = tid; e < (long long)m * n; e += BLOCK) A[e] = Ag[e];
+  for (int j = tid; j < n; j += BLOCK) jp[j] = j;
+  __syncthreads();
+  column_norms(A, n, 0, m, 0, n, false, vn1, vn2, s_w);
+  for (int k = 0; k < K; k++) {
+    // pivot search, with the downdating that step k-1 left to do folded into it: a strided scan (a thread meets its
+    // positions in ascending order), then waves, then the block.  The barrier of the block reduction also carries
+    // "some column wants its norm recomputed"; then those norms are recomputed and the search is made again.
+    T best = T(-2);
+    int p = n, recompute = 0;
+    for (int j = k + tid; j < n; j += BLOCK) {
+      T v = vn1[j];
+      if (k > 0 && v != T(0)) {
+        const T r = dabs(A[(long long)(k - 1) * n + j]) / v;
+        T t = T(1) - r * r;
+        t = t > T(0) ? t : T(0);
+        const T q = v / vn2[j];
+        if (t * (q * q) <= tol3z) { vn2[j] = T(-1); recompute = 1; }
+        else vn1[j] = v = v * sqrt(t);
+      }
+      argmax_take(best, p, v == v ? v : T(-1), j);
+    }
+    for (int pass = 0; pass < 2; pass++) {
+      wave_argmax(best, p);
+      if ((tid & 63) == 0) { s_red[tid >> 6] = best; s_pos[tid >> 6] = p; }
+      if (!__syncthreads_or(recompute)) break;  // (pass 1 arrives with recompute = 0)
+      column_norms(A, n, k, m, k, n, true, vn1, vn2, s_w);
+      recompute = 0;
+      best = T(-2); p = n;
+      for (int j = k + tid; j < n; j += BLOCK) {
+        const T v = vn1[j];
+        argmax_take(best, p, v == v ? v : T(-1), j);
+      }
+    }
+    best = s_red[0]; p = s_pos[0];
+#pragma unroll
+    for (int w = 1; w < BLOCK / 64; w++) argmax_take(best, p, s_red[w], s_pos[w]);
+    // (thread 0 scanned position k itself, so k <= p < n whatever the norms hold)
+    // the swap and the squared norm of the new column k below the diagonal, in one pass over the rows
+    T part = T(0);
+    for (int i = tid; i < m; i += BLOCK) {
+      const T a = A[(long long)i * n + p];
+      if (p != k) {
+        A[(long long)i * n + p] = A[(long long)i * n + k];
+        A[(long long)i * n + k] = a;
+      }
+      if (i > k) part += a * a;
+    }
+    if (p != k && tid == 0) {
+      const int jt = jp[p]; jp[p] = jp[k]; jp[k] = jt;
+      vn1[p] = vn1[k]; vn2[p] = vn2[k];
+    }
+    const T xn2 = block_sum(part, s_red);
+    const T alpha = A[(long long)k * n + k];
+    if (xn2 == T(0)) {  // dlarfg: H = I
+      if (tid == 0) tau[k] = T(0);
+    } else {
+      const T nrm = hypot(alpha, sqrt(xn2));
+      const T beta = alpha >= T(0) ? -nrm : nrm;
+      const T tk = (beta - alpha) / beta;
+      const T scale = T(1) / (alpha - beta);
+      __syncthreads();  // (every thread has read alpha)
+      for (int i = k + 1 + tid; i < m; i += BLOCK) A[(long long)i * n + k] *= scale;
+      if (tid == 0) { A[(long long)k * n + k] = beta; tau[k] = tk; }
+      if (k + 1 < n) apply_reflector(A, n, k, m, k + 1, n, A, n, k, tk, s_v, s_w, VM);
+    }
+    __syncthreads();
+  }
+  __syncthreads();
+  for (int j = tid; j < n; j += BLOCK) jpvt[j] = jp[j];
+  if (use_lds)
+    for (long long e = tid; e < (long long)m * n; e += BLOCK) Ag[e] = A[e];
 }
 
 // Q (m x nc) = H_0 H_1 ... H_{k-1} applied to the first nc columns of the identity (dorg2r)
@@ -539,6 +695,36 @@ template <class T> int geqrf_typed(long long batch, int m, int n, void* A, void*
   return pthip::post_launch("geqrf");
 }
 
+// the two partial-norm vectors and the permutation ride in dynamic LDS in both forms; beside the global form's
+// s_v[VMAX] that leaves room for QP3_VEC_MAX bytes of them (n <= 5939 fp64 / 9898 fp32 columns)
+constexpr size_t QP3_VEC_MAX = QR_LDS_MAX - VMAX * sizeof(double);
+
+template <class T> int geqp3_typed(long long batch, int m, int n, void* A, void* tau, void* jpvt) {
+  const size_t vec = (size_t)n * (2 * sizeof(T) + sizeof(int));
+  const size_t need = (size_t)m * n * sizeof(T) + vec;
+  if (need <= QR_LDS_MAX && m <= 512 && !qr_no_lds) {
+    auto k = geqp3_kernel<T, 512>;
+    static bool attr = false;
+    if (!attr) {
+      PTHIP_CHECK(hipFuncSetAttribute((const void*)k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)QR_LDS_MAX));
+      attr = true;
+    }
+    PTHIP_KLAUNCH(k, dim3((unsigned)batch), dim3(BLOCK), need, pthip::ctx().stream, (T*)A, (T*)tau, (int*)jpvt, m, n, 1);
+    return pthip::post_launch("geqp3(lds)");
+  }
+  if (vec > QP3_VEC_MAX)
+    return pthip::set_error("pthip_geqp3: n = %d columns: the norm and permutation vectors (%zu bytes) do not fit the LDS (%zu)", n, vec,
+                            QP3_VEC_MAX);
+  auto k = geqp3_kernel<T, VMAX>;
+  static bool attr = false;
+  if (!attr) {
+    PTHIP_CHECK(hipFuncSetAttribute((const void*)k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)QP3_VEC_MAX));
+    attr = true;
+  }
+  PTHIP_KLAUNCH(k, dim3((unsigned)batch), dim3(BLOCK), vec, pthip::ctx().stream, (T*)A, (T*)tau, (int*)jpvt, m, n, 0);
+  return pthip::post_launch("geqp3");
+}
+
 template <class T> int orgqr_typed(long long batch, int m, int nc, int k, const void* QR, long long ldqr, long long stride,
                                    const void* tau, void* Q) {
   const size_t need = (size_t)m * nc * sizeof(T);
@@ -571,6 +757,14 @@ extern "C" int pthip_geqrf(int dtype, int64_t batch, int64_t m, int64_t n, void*
   if (dtype == PTHIP_F64) return geqrf_typed<double>(batch, (int)m, (int)n, A, tau);
   if (dtype == PTHIP_F32) return geqrf_typed<float>(batch, (int)m, (int)n, A, tau);
   return pthip::set_error("pthip_geqrf: dtype %d not supported (float32/float64 only)", dtype);
+}
+
+extern "C" int pthip_geqp3(int dtype, int64_t batch, int64_t m, int64_t n, void* A, void* tau, void* jpvt) {
+  PTHIP_REQUIRE_INIT();
+  if (batch <= 0 || m <= 0 || n <= 0) return 0;
+  if (dtype == PTHIP_F64) return geqp3_typed<double>(batch, (int)m, (int)n, A, tau, jpvt);
+  if (dtype == PTHIP_F32) return geqp3_typed<float>(batch, (int)m, (int)n, A, tau, jpvt);
+  return pthip::set_error("pthip_geqp3: dtype %d not supported (float32/float64 only)", dtype);
 }
 
 extern "C" int pthip_orgqr(int dtype, int64_t batch, int64_t m, int64_t ncols, int64_t k, const void* QR, int64_t ldqr,

@@ -6,7 +6,8 @@ Reference: linalg/decomposition/qr.py:20 (perform 153-221: geqrf + orgqr), decom
 solvers/lstsq.py:10 ``Lstsq`` (np.linalg.lstsq), 39 ``TensorSolve``, solvers/tridiagonal.py:18, 92
 (gttrf / gttrs), decomposition/eigen.py:363 ``Eigvalsh``, constructors.py:52 ``BlockDiagonal``
 (scipy.linalg.block_diag).  Kernels: csrc/decomp.hip (correct-first tier).
-Leading batch dimensions arrive through ``Blockwise`` (dispatch/linalg.py loops the items).
+Leading batch dimensions arrive through ``Blockwise`` (dispatch/linalg.py loops the items; the column-pivoted
+``QR`` takes the whole stack in one launch of each of its kernels).
 """
 
 from __future__ import annotations
@@ -54,39 +55,97 @@ def geqrf_device(env, x: DeviceArray):
     return qr, tau
 
 
+QR_LDS_MAX = 160 * 1024 - 12 * 1024  # (csrc/decomp.hip)
+
+
+def geqp3_lds_fits(m: int, n: int, itemsize: int) -> bool:
+    """Whether ``pthip_geqp3`` keeps an m x n matrix in LDS (beside the two norm vectors and the permutation) or
+    leaves it in global memory: the bound of csrc/decomp.hip ``geqp3_typed``, for tests and tools that want to sit
+    on either side of it.  (``PTHIP_QR_NO_LDS`` forces the global form whatever this says.)"""
+    return m <= 512 and m * n * itemsize + n * (2 * itemsize + 4) <= QR_LDS_MAX
+
+
+def geqp3_device(env, x: DeviceArray):
+    """(packed factors, tau, jpvt) — LAPACK's geqp3 on a copy of ``x`` (..., m, n): A P = Q R with the leading batch
+    dimensions flattened into one launch; jpvt (..., n) int32, 0-based.  A broadcast (stride-0) operand is
+    materialised by the copy."""
+    *lead, m, n = x.shape
+    nb = int(np.prod(lead)) if lead else 1
+    qr = x.contiguous_copy()
+    tau = DeviceArray.empty((*lead, min(m, n)), x.dtype)
+    jpvt = DeviceArray.empty((*lead, n), np.dtype("int32"))
+    ffi.check(env.lib.pthip_geqp3(_dt(x), nb, m, n, qr.ptr, tau.ptr, jpvt.ptr))
+    return qr, tau, jpvt
+
+
 def orgqr_device(env, qr: DeviceArray, tau: DeviceArray, ncols: int) -> DeviceArray:
-    m, n = qr.shape
-    q = DeviceArray.empty((m, ncols), qr.dtype)
-    ffi.check(env.lib.pthip_orgqr(_dt(qr), 1, m, ncols, tau.shape[0], qr.ptr, n, m * n, tau.ptr, q.ptr))
+    """Q (..., m, ncols) of the packed factors ``qr`` (..., m, n) and ``tau`` (..., k): one launch for the stack"""
+    *lead, m, n = qr.shape
+    nb = int(np.prod(lead)) if lead else 1
+    q = DeviceArray.empty((*lead, m, ncols), qr.dtype)
+    ffi.check(env.lib.pthip_orgqr(_dt(qr), nb, m, ncols, tau.shape[-1], qr.ptr, n, m * n, tau.ptr, q.ptr))
     return q
 
 
 def _triu(env, qr: DeviceArray, rows: int, lower=False, unit=False) -> DeviceArray:
-    m, n = qr.shape
-    r = DeviceArray.empty((rows, n), qr.dtype)
-    ffi.check(env.lib.pthip_triu(_dt(qr), 1, rows, n, qr.ptr, n, m * n, r.ptr, int(lower), int(unit)))
+    *lead, m, n = qr.shape
+    nb = int(np.prod(lead)) if lead else 1
+    r = DeviceArray.empty((*lead, rows, n), qr.dtype)
+    ffi.check(env.lib.pthip_triu(_dt(qr), nb, rows, n, qr.ptr, n, m * n, r.ptr, int(lower), int(unit)))
     return r
+
+
+def _geqp3_empty(m: int, n: int, dtype) -> None:
+    """An empty operand launches nothing; what happens instead is whatever the reference's ``QR.perform`` does with
+    it, which is LAPACK's own argument check.  SciPy 1.15: n = 0 returns (empty factors, an empty permutation, and
+    for mode "full" the m x m identity — the code below gives exactly that), while m = 0 with n > 0 raises f2py's
+    ``_flapack.error`` ("(lwork>=n||lwork==-1) failed for 1st keyword lwork: dgeqp3:lwork=0": the workspace query
+    answers 0).  That class has no public name, so the same two calls are made here on an empty host array of the
+    operand's shape — no device data is read — and raise it, type and message, themselves."""
+    import scipy.linalg
+
+    a = np.empty((m, n), dtype=dtype)
+    (geqp3,) = scipy.linalg.get_lapack_funcs(("geqp3",), (a,))
+    *_, work, _info = geqp3(a, lwork=-1)
+    geqp3(a, lwork=work.item())
 
 
 @handler("QR")
 def qr_op(node, inputs, env):
+    """``QR.perform``.  With ``pivoting`` (geqp3) the operand may carry leading batch dimensions (``Blockwise``
+    hands the whole stack over: every kernel takes a batch count) and the permutation is the last output."""
     mode = node.params["mode"]
-    x = _matrix(env, inputs[0], "QR")
-    m, n = x.shape
-    qr, tau = geqrf_device(env, x)
+    pivoting = bool(node.params.get("pivoting", False))
+    if pivoting:
+        from pytensor_amd.dispatch.linalg import _lapack_operands
+
+        (x,) = _lapack_operands(env, "QR", inputs[0])
+        if x.ndim < 2:
+            raise np.linalg.LinAlgError(f"QR: {x.ndim}-dimensional array given. Array must be at least two-dimensional")
+    else:
+        x = _matrix(env, inputs[0], "QR")
+    m, n = x.shape[-2:]
+    if pivoting:
+        if m == 0 or n == 0:
+            _geqp3_empty(m, n, x.dtype)
+        qr, tau, jpvt = geqp3_device(env, x)
+        P = [jpvt]
+    else:
+        qr, tau = geqrf_device(env, x)
+        P = []
     # perform 171-174: economic / raw keep the leading n rows of R when m >= n
     R = _triu(env, qr, m if (mode not in ("economic", "raw") or m < n) else n)
     if mode == "r":
-        return [R]
+        return [R, *P]
     if mode == "raw":
-        return [qr, tau, R]
+        return [qr, tau, R, *P]
     if m < n:
         Q = orgqr_device(env, qr, tau, m)
     elif mode == "economic":
         Q = orgqr_device(env, qr, tau, n)
     else:
         Q = orgqr_device(env, qr, tau, m)
-    return [Q, R]
+    return [Q, R, *P]
 
 
 # ---- SVD ------------------------------------------------------------------------------------------

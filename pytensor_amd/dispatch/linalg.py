@@ -193,6 +193,10 @@ def blockwise(node, inputs, env):
         from pytensor_amd.dispatch import lu
 
         return lu.eigh(type("_N", (), {"params": cp}), ins, env)
+    if p["core_op"] == "QR" and cp.get("pivoting"):  # (geqp3, orgqr and triu each take the whole stack in one launch)
+        from pytensor_amd.dispatch import decomp
+
+        return decomp.qr_op(type("_N", (), {"params": cp}), ins, env)
     if p["core_op"] == "SolveDiscreteARE":  # (one launch for the whole batch up to m = 64)
         from pytensor_amd.dispatch import riccati
 

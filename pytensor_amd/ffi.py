@@ -135,6 +135,7 @@ SIGNATURES = {
     "pthip_convolve1d": (_int, [_int, _i64, _vp, _i64, _vp, _int, _vp]),
     "pthip_convolve2d": (_int, [_int, _i64, _i64, _vp, _i64, _i64, _vp, _int, _vp]),
     "pthip_geqrf": (_int, [_int, _i64, _i64, _i64, _vp, _vp]),
+    "pthip_geqp3": (_int, [_int, _i64, _i64, _i64, _vp, _vp, _vp]),
     "pthip_orgqr": (_int, [_int, _i64, _i64, _i64, _i64, _vp, _i64, _i64, _vp, _vp]),
     "pthip_svd_rows": (_int, [_int, _i64, _i64, _i64, _int, _vp, _vp, _vp, _vp, _vp]),
     "pthip_fill_null_rows": (_int, [_int, _i64, _i64, _i64, _vp, _vp, _i64, _vp, _i64]),

@@ -384,7 +384,9 @@ def _register_extra_ops():
     @hip_funcify.register(QR)
     def _(op, node, ctx):
         if op.pivoting:
-            return None  # (geqp3's column pivoting: not lowered)
+            # geqp3: one more output, the int32 permutation, last.  The key is emitted only when true: unpivoted
+            # nodes keep exactly the params they always had
+            return "QR", {"mode": str(op.mode), "pivoting": True}
         return "QR", {"mode": str(op.mode)}
 
     @hip_funcify.register(SVD)
