@@ -62,6 +62,11 @@ template <class P> static __device__ __forceinline__ P pthip_nt_pack(const P* p)
 """
 
 
+def nt_loads() -> bool:
+    """Whether streamed-once operands are read with non-temporal loads (``PTHIP_NT_LOADS=0``: plain loads)."""
+    return os.environ.get("PTHIP_NT_LOADS", "1") != "0"
+
+
 def _stream_load(ptr_expr: str, struct=False) -> str:
     """Load of an operand that is streamed once (the vector inputs of a flat fused kernel, the
     matrix of ``gchain``): non-temporal (``nt``) — the line is not retained in L2/MALL, which is
@@ -69,7 +74,7 @@ def _stream_load(ptr_expr: str, struct=False) -> str:
     (profiles/r2f_nt_loads.txt): ``gchain`` 184.5 -> 171.2 us (5.64 -> 6.08 TB/s), config #4
     4072 -> 4366 evals/s; 52-op Composite+Sum at N=1e7 39.9 -> 38.1 us.  ``PTHIP_NT_LOADS=0``
     restores plain loads."""
-    if os.environ.get("PTHIP_NT_LOADS", "1") != "0":
+    if nt_loads():
         if struct:  # the pack types are structs: reinterpret as one 16/8/4-byte word
             return f"pthip_nt_pack({ptr_expr})"
         return f"__builtin_nontemporal_load({ptr_expr})"

@@ -29,6 +29,14 @@ CHAIN_RG = int(os.environ.get("PTHIP_CHAIN_RG", 0))  # 0 = auto
 # on C4 (evals/s): 448: 3252, 480: 3220, 512: 3209, 1024: 3274, 2048: 3331, 4096: 3282 —
 # a persistent grid that leaves CUs free for the overlapped latency chain does not pay.
 CHAIN_GRID = int(os.environ.get("PTHIP_CHAIN_GRID", 2048))
+# The software-pipelined row loop of the one-pass kernel (csrc/gchain_device.h): the next half group's loads are in
+# flight while a half is reduced.  0 (``PTHIP_GCHAIN_PIPE=0``) selects the plain loop — same bits, the A/B reference.
+PTHIP_GCHAIN_PIPE = os.environ.get("PTHIP_GCHAIN_PIPE", "1") != "0"
+# The pipelined form gathers from a copy of the table in LDS (a read from memory would queue behind the prefetch).
+# 128 entries (1 KiB) is the size it was timed with; the kernel itself takes any table that fits beside the block
+# combine's 4 KiB per 128 columns inside CHAIN_LDS_BUDGET (what tests/test_gchain_codegen.py holds every instance to).
+GATHER_LDS_ENTRIES = 128
+CHAIN_LDS_BUDGET = 48 * 1024
 MAX_SCATTER_BINS = 256  # 64 bins per accumulator register of a lane, up to four (codegen_gchain.gemv_chain_source)
 MAX_CHAIN_K = 4096  # columns the one-pass kernel holds in registers (32 chunks of 128: one row per group)
 
@@ -162,7 +170,14 @@ def gemv_chain(node, inputs, env):
     if scatter_out is not None:
         sgroups = max(1, (base.shape[0] + 63) // 64)
         name += f"_b{sgroups}"
-    src = codegen_gchain.gemv_chain_source(name, body, e_modes, rs, w_out, C, RG, store_r, y1d is not None, out_store, scatter_out, sgroups, pack, atype)
+    tables = [v[0] for v in e_vals if isinstance(v, tuple)]
+    pipe = PTHIP_GCHAIN_PIPE and _pipelined(atype, C, RG, pack, scatter_out, sgroups, tables)
+    lds_bytes, full = 0, False
+    if pipe:
+        full = K == 128 * C  # no lane past the end of a row: loads without the column predicate
+        name += "_pipef" if full else "_pipe"
+        lds_bytes = sum(t.shape[0] * t.itemsize for t in tables)  # the gather table's copy (dynamic LDS)
+    src = codegen_gchain.gemv_chain_source(name, body, e_modes, rs, w_out, C, RG, store_r, y1d is not None, out_store, scatter_out, sgroups, pack, atype, pipe, full)
     fn = kernel_cache.get_function(src, name)
     ngroups = (N + RG - 1) // RG
     grid = max(1, min((ngroups + 3) // 4, CHAIN_GRID))
@@ -197,7 +212,7 @@ def gemv_chain(node, inputs, env):
     buf = struct.pack("<" + "".join(a[0] for a in args), *[a[1] for a in args])
     kt = env.kernel_timer
     tok = kt.begin() if kt is not None else None
-    ffi.check(env.lib.pthip_launch(fn, grid, 1, 1, BLOCK, 1, 1, 0, buf, len(buf)))
+    ffi.check(env.lib.pthip_launch(fn, grid, 1, 1, BLOCK, 1, 1, lds_bytes, buf, len(buf)))
     if kt is not None:
         kt.end(name, tok)
     finals = finish_partials(env, spec, parts, grid, p.get("defer_reduce") or ())
@@ -212,6 +227,20 @@ def gemv_chain(node, inputs, env):
         if late_forced:
             res[(1 if store_r else 0) + scatter_pos] = None  # (nothing outside the node reads it: stored only for the scatter)
     return res
+
+
+def _pipelined(atype, C, RG, pack, scatter_out, sgroups, tables) -> bool:
+    """Whether this instance runs the pipelined row loop: only the instances that were timed on the device against the
+    plain loop and gained (profiles/r10_gchain_sweep.txt: float64, one 128-column chunk in 16-byte packs — K = 64, 100,
+    128 —, the scatter in two bin groups, a gather table of 128 entries).  The generator emits the pipelined form for
+    any ``RG`` >= 4, either pack, float32 and any bin count, and gives the plain loop's bits there too, but K = 127
+    (two 8-byte loads per chunk) and K = 256 measured no gain, K = 1024 needs 268 registers (one wave per SIMD where
+    the plain loop runs two), and the rest was not timed: they keep the plain loop until a measurement says otherwise."""
+    if atype != "float64" or C != 1 or RG != 32 or pack != 2:
+        return False
+    if scatter_out is None or sgroups != 2:
+        return False
+    return len(tables) == 1 and tables[0].shape[0] <= GATHER_LDS_ENTRIES
 
 
 _STATUS = [None]
