@@ -396,6 +396,21 @@ int pthip_gesv_batched(int dtype, int64_t batch, int64_t n, int64_t nrhs, const 
  * one-launch tier). */
 int pthip_laswp_batched(int dtype, int64_t batch, int64_t n, int64_t nrhs, const void* B, int64_t sBb,
                         const void* perm, int64_t sPb, void* out);
+/* Banded solves (LAPACK gbsv behind scipy.linalg.solve(assume_a="banded"), solvers/general.py Solve.perform), the
+ * band found on the device.  pthip_band_scan: band[2b], band[2b+1] (int32) = the lower and upper bandwidth of A[b]
+ * as scipy.linalg.bandwidth finds them (max i-j / j-i over entries that are not exactly zero; a NaN is not zero);
+ * A[b] is read at A + b*sAb + i*sA0 + j*sA1 (elements).  The call zeroes band itself, in the stream.
+ * pthip_gbsv_batched: X[b] (n x nrhs, contiguous) = A[b]^-1 B[b] by LU with partial pivoting inside the band that
+ * band holds for the item (sAb = 0: one matrix for the whole batch, and band[0], band[1] describe it), B[b]
+ * (n x nrhs row-major) at B + b*sBb.  An item whose working band ((2 kl + ku + 1) x n) does not fit the LDS works in
+ * its n x n slab of ws: pass pthip_gbsv_workspace(dtype, batch, n) bytes (0 when every band of that order fits).
+ * An exactly zero or NaN pivot NaN-fills the item's X and leaves its neighbours alone. */
+int pthip_band_scan(int dtype, int64_t batch, int64_t n, const void* A, int64_t sAb, int64_t sA0, int64_t sA1,
+                    void* band);
+size_t pthip_gbsv_workspace(int dtype, int64_t batch, int64_t n);
+int pthip_gbsv_batched(int dtype, int64_t batch, int64_t n, int64_t nrhs, const void* A, int64_t sAb,
+                       int64_t sA0, int64_t sA1, const void* B, int64_t sBb, void* X, const void* band,
+                       void* ws, size_t ws_bytes);
 
 /* ---- indexing / data movement (bit-exact tier; pytensor/tensor/subtensor.py:868-2614,
  *      pytensor/tensor/basic.py:1545 Alloc, 2405 Join, compile/ops.py:121 DeepCopyOp) ---- */

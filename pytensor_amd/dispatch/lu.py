@@ -1,4 +1,4 @@
-"""General dense solves on LU with partial pivoting: ``Solve`` (gen / pos), ``Det``, ``SLogDet``,
+"""General dense solves on LU with partial pivoting: ``Solve`` (gen / pos / banded), ``Det``, ``SLogDet``,
 ``MatrixInverse`` and their ``Blockwise`` batching.
 
 Reference: pytensor/tensor/linalg/solvers/general.py:17 ``Solve`` (perform 62-75:
@@ -183,6 +183,61 @@ def solve_general(env, A: DeviceArray, b: DeviceArray, b_ndim: int) -> DeviceArr
     return out
 
 
+def banded_tier(n: int, nb: int) -> str:
+    """How ``Solve(assume_a="banded")`` of ``nb`` systems of order ``n`` runs, from the shapes alone (the bandwidths
+    are data and never reach the host):
+
+    ``"wave"``  n <= 64: the one-launch dense tier of ``solve_tier`` — one launch and the same n^2 read as a band
+                scan; partial pivoting on the dense rows picks gbsv's pivots (what lies outside the band is zero).
+    ``"band"``  n > 64, any ``nb``: ``pthip_band_scan`` then ``pthip_gbsv_batched`` (csrc/gbsv.hip), two launches."""
+    return "wave" if n <= WAVE_MAX_N else "band"
+
+
+def _gbsv(env, A: DeviceArray, b: DeviceArray, b_ndim: int, out: DeviceArray, bshape):
+    """``out`` (contiguous, (*bshape, *core)) = A^-1 b through the band kernels.  The batch dims go to the kernels
+    as strides, as in ``_gesv_wave``: nothing is copied, a matrix shared by the batch (stride 0) is scanned once, and
+    dims that do not fold into one stride are walked here."""
+    n = A.shape[-1]
+    nrhs = 1 if b_ndim == 1 else b.shape[-1]
+    core_b = b.shape[b.ndim - b_ndim :]
+    if any(s != 1 and st != c for s, st, c in zip(core_b, b.strides[b.ndim - b_ndim :], contiguous_strides(core_b))):
+        b = b.contiguous()
+    outer, inner, st = _collapse_batch(bshape, _batch_strides(A, 2, bshape), _batch_strides(b, b_ndim, bshape))
+    isz, per = A.itemsize, n * nrhs
+    scanned = 1 if st[0] == 0 else inner
+    band = DeviceArray.empty((scanned, 2), "int32")
+    # a band that does not fit the LDS works in a dense slab per item: what the LU copy of the general path costs
+    ws_bytes = int(env.lib.pthip_gbsv_workspace(_dt(A), inner, n))
+    ws = DeviceArray.empty((ws_bytes,), "uint8") if ws_bytes else None
+    for f, idx in enumerate(np.ndindex(*[s for s, _ in outer])):
+        offs = [sum(i * sts[k] for i, (_, sts) in zip(idx, outer)) for k in range(2)]
+        ffi.check(env.lib.pthip_band_scan(_dt(A), scanned, n, A.ptr + offs[0] * isz, st[0], A.strides[-2], A.strides[-1], band.ptr))
+        ffi.check(env.lib.pthip_gbsv_batched(
+            _dt(A), inner, n, nrhs, A.ptr + offs[0] * isz, st[0], A.strides[-2], A.strides[-1], b.ptr + offs[1] * isz, st[1],
+            out.ptr + f * inner * per * isz, band.ptr, None if ws is None else ws.ptr, ws_bytes))
+
+
+def solve_banded(env, A: DeviceArray, b: DeviceArray, b_ndim: int) -> DeviceArray:
+    """x = A^-1 b with each item's bandwidths found from its data, by the tier ``banded_tier`` names.  ``lower`` plays
+    no part (scipy ignores it); a zero or NaN pivot NaN-fills the item, as in ``solve_general``."""
+    n = A.shape[-1]
+    if A.shape[-2] != n:
+        raise ValueError("Solve: expected a square matrix")
+    if b.shape[b.ndim - b_ndim] != n:
+        raise ValueError(f"Solve: incompatible shapes {A.shape} and {b.shape}")
+    if str(b.dtype) != str(A.dtype):
+        raise TypeError("Solve: dtype mismatch")
+    bshape = tuple(np.broadcast_shapes(A.shape[:-2], b.shape[: b.ndim - b_ndim]))
+    nb = int(np.prod(bshape)) if bshape else 1
+    out = DeviceArray.empty((*bshape, *b.shape[b.ndim - b_ndim :]), b.dtype)
+    if out.size:
+        if banded_tier(n, nb) == "wave":
+            _gesv_wave(env, A, b, b_ndim, out, bshape, False)
+        else:
+            _gbsv(env, A, b, b_ndim, out, bshape)
+    return out
+
+
 def _solve(env, p, A, b):
     from pytensor_amd.dispatch.linalg import _lapack_operands
 
@@ -201,6 +256,8 @@ def _solve(env, p, A, b):
         from pytensor_amd.dispatch.decomp import solve_tridiagonal
 
         return solve_tridiagonal(env, A, b, p["b_ndim"])
+    if assume == "banded":
+        return solve_banded(env, A, b, p["b_ndim"])
     raise NotImplementedError(f"hip linker: Solve(assume_a={assume!r}) is not lowered")
 
 

@@ -146,6 +146,9 @@ SIGNATURES = {
     "pthip_trsm": (_int, [_int, _int, _int, _int, _i64, _i64, _i64, _vp, _i64, _i64, _i64, _vp, _i64, _vp]),
     "pthip_gesv_batched": (_int, [_int, _i64, _i64, _i64, _vp, _i64, _i64, _i64, _vp, _i64, _vp, _int]),
     "pthip_laswp_batched": (_int, [_int, _i64, _i64, _i64, _vp, _i64, _vp, _i64, _vp]),
+    "pthip_band_scan": (_int, [_int, _i64, _i64, _vp, _i64, _i64, _i64, _vp]),
+    "pthip_gbsv_workspace": (_sz, [_int, _i64, _i64]),
+    "pthip_gbsv_batched": (_int, [_int, _i64, _i64, _i64, _vp, _i64, _i64, _i64, _vp, _i64, _vp, _vp, _vp, _sz]),
     "pthip_copy_strided": (_int, [_int, _int, C.POINTER(_i64), _vp, C.POINTER(_i64), _vp, C.POINTER(_i64)]),
     "pthip_take_rows": (_int, [_int, _i64, _i64, _vp, _i64, _i64, _vp, _vp]),
     "pthip_scatter_rows_workspace": (_sz, [_i64, _i64, _i64]),

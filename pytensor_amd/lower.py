@@ -336,7 +336,7 @@ def _register_extra_ops():
     def _(op, node, ctx):
         # "sym"/"her" (real dtypes: the same thing) run on the general LU — LAPACK's sysv
         # (Bunch-Kaufman) is a different but equally backward-stable factorisation
-        if op.assume_a not in ("gen", "pos", "sym", "her", "tridiagonal"):
+        if op.assume_a not in ("gen", "pos", "sym", "her", "tridiagonal", "banded"):
             return None
         return "Solve", {"assume_a": str(op.assume_a), "lower": bool(op.lower), "b_ndim": int(op.b_ndim)}
 
