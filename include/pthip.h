@@ -363,6 +363,16 @@ int pthip_svd_rows(int dtype, int64_t batch, int64_t r, int64_t c, int vectors, 
  * i of Q (c x ldq): an orthonormal completion of a rank-deficient or economy-sized factor */
 int pthip_fill_null_rows(int dtype, int64_t batch, int64_t r, int64_t c, void* Wt, const void* S, int64_t r_valid,
                          const void* Q, int64_t ldq);
+/* Blockwise(SVD) / Blockwise(MatrixPinv) of small matrices in one launch (csrc/svd_batched.hip), max(m, n) <= 64: one
+ * lane group of a wavefront per matrix, one-sided Jacobi in registers.  A[b] (m x n) is read at A + b*sAb + i*sA0 +
+ * j*sA1 (elements; any strides, sAb = 0: one matrix for the whole batch).  job 0: S[b] (min(m, n), descending) alone;
+ * job 1: U[b] (m x k), S[b], Vt[b] (k x n), k = min(m, n); job 2: U[b] (m x m), S[b], Vt[b] (n x n); job 3: pinv[b]
+ * (n x m) with np.linalg.pinv's cut-off s > rcond * s_max.  Every output is contiguous and in its final layout;
+ * outputs a job does not produce may be NULL.  Vectors of a zero singular value (and job 2's complement) are an
+ * orthonormal completion.  An item holding a NaN or an Inf is all NaN in every output and leaves its neighbours
+ * alone.  Non-convergence (60 sweeps) raises bit 2 of the device error word, like pthip_svd_rows. */
+int pthip_gesvj_batched(int dtype, int64_t batch, int64_t m, int64_t n, int job, const void* A, int64_t sAb,
+                        int64_t sA0, int64_t sA1, double rcond, void* U, void* S, void* Vt, void* pinv);
 /* dst (rows x cols, contiguous) = the upper (lower != 0: lower) triangle of the leading rows of src
  * (row stride ld, src_stride between batch items), zeros elsewhere, the diagonal 1 if unit_diag:
  * the R of QR.perform (qr.py:171-174), the L and U of LU.perform (lu.py:77-89) */

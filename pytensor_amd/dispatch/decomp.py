@@ -6,8 +6,9 @@ Reference: linalg/decomposition/qr.py:20 (perform 153-221: geqrf + orgqr), decom
 solvers/lstsq.py:10 ``Lstsq`` (np.linalg.lstsq), 39 ``TensorSolve``, solvers/tridiagonal.py:18, 92
 (gttrf / gttrs), decomposition/eigen.py:363 ``Eigvalsh``, constructors.py:52 ``BlockDiagonal``
 (scipy.linalg.block_diag).  Kernels: csrc/decomp.hip (correct-first tier).
-Leading batch dimensions arrive through ``Blockwise`` (dispatch/linalg.py loops the items; the column-pivoted
-``QR`` takes the whole stack in one launch of each of its kernels).
+Leading batch dimensions arrive through ``Blockwise``: ``QR`` (pivoted or not), ``SVD`` and ``MatrixPinv`` take the
+whole stack — ``svd_tier``: one launch of csrc/svd_batched.hip up to max(m, n) = 64, the kernels of the single matrix
+launched once each over the stack above it; dispatch/linalg.py loops the items of the other ops here.
 """
 
 from __future__ import annotations
@@ -47,11 +48,13 @@ def _matrix(env, v, what):
 
 # ---- QR -------------------------------------------------------------------------------------------
 def geqrf_device(env, x: DeviceArray):
-    """(packed factors m x n, tau[min(m, n)]) — LAPACK's geqrf on a copy of ``x``"""
-    m, n = x.shape
+    """(packed factors, tau) — LAPACK's geqrf on a copy of ``x`` (..., m, n), the leading batch dimensions flattened
+    into one launch like ``geqp3_device``; tau (..., min(m, n))"""
+    *lead, m, n = x.shape
+    nb = int(np.prod(lead)) if lead else 1
     qr = x.contiguous_copy()
-    tau = DeviceArray.empty((min(m, n),), x.dtype)
-    ffi.check(env.lib.pthip_geqrf(_dt(x), 1, m, n, qr.ptr, tau.ptr))
+    tau = DeviceArray.empty((*lead, min(m, n)), x.dtype)
+    ffi.check(env.lib.pthip_geqrf(_dt(x), nb, m, n, qr.ptr, tau.ptr))
     return qr, tau
 
 
@@ -112,18 +115,15 @@ def _geqp3_empty(m: int, n: int, dtype) -> None:
 
 @handler("QR")
 def qr_op(node, inputs, env):
-    """``QR.perform``.  With ``pivoting`` (geqp3) the operand may carry leading batch dimensions (``Blockwise``
-    hands the whole stack over: every kernel takes a batch count) and the permutation is the last output."""
+    """``QR.perform``.  The operand may carry leading batch dimensions (``Blockwise`` hands the whole stack over:
+    every kernel takes a batch count); with ``pivoting`` (geqp3) the permutation is the last output."""
+    from pytensor_amd.dispatch.linalg import _lapack_operands
+
     mode = node.params["mode"]
     pivoting = bool(node.params.get("pivoting", False))
-    if pivoting:
-        from pytensor_amd.dispatch.linalg import _lapack_operands
-
-        (x,) = _lapack_operands(env, "QR", inputs[0])
-        if x.ndim < 2:
-            raise np.linalg.LinAlgError(f"QR: {x.ndim}-dimensional array given. Array must be at least two-dimensional")
-    else:
-        x = _matrix(env, inputs[0], "QR")
+    (x,) = _lapack_operands(env, "QR", inputs[0])
+    if x.ndim < 2:
+        raise np.linalg.LinAlgError(f"QR: {x.ndim}-dimensional array given. Array must be at least two-dimensional")
     m, n = x.shape[-2:]
     if pivoting:
         if m == 0 or n == 0:
@@ -153,6 +153,8 @@ def svd_device(env, x: DeviceArray, full_matrices: bool, compute_uv: bool):
     """(U, S, Vt) or S alone.  One-sided Jacobi on the rows of the wide orientation of ``x``
     (csrc/decomp.hip); the tall factor's null / complementary directions are completed from a
     Householder Q, which LAPACK leaves just as arbitrary."""
+    if x.ndim > 2:
+        return _svd_stack(env, x, full_matrices, compute_uv)
     m, n = x.shape
     tall = m >= n
     X = (_t(x).contiguous_copy() if tall else x.contiguous_copy())  # r x c, r <= c
@@ -188,6 +190,161 @@ def svd_device(env, x: DeviceArray, full_matrices: bool, compute_uv: bool):
     if tall:  # x^T = P S Wt  ->  x = Wt^T S P^T
         return [_t(big).contiguous(), S, Pt]
     return [_t(Pt).contiguous(), S, big]
+
+
+SVD_WAVE_MAX = 64  # max(m, n) of the one-launch tier (csrc/svd_batched.hip)
+SVD_ROWS_MAX = 2048  # min(m, n) of pthip_svd_rows
+PINV_RCOND = 1e-15  # np.linalg.pinv's default
+
+
+def svd_tier(m: int, n: int, nb: int):
+    """The tier that takes a stack of ``nb`` m x n matrices, from the shapes alone: "wave" (one lane group per matrix,
+    one launch) up to max(m, n) = 64, "rows" (one ``pthip_svd_rows`` workgroup per matrix, the batch in grid.x, and the
+    batched completion) above that up to min(m, n) = 2048, None (refused) beyond."""
+    if max(m, n) <= SVD_WAVE_MAX:
+        return "wave"
+    if min(m, n) <= SVD_ROWS_MAX:
+        return "rows"
+    return None
+
+
+def _tb(x: DeviceArray) -> DeviceArray:
+    """the stack with its two core dimensions swapped (a view)"""
+    return x.view((*x.shape[:-2], x.shape[-1], x.shape[-2]), (*x.strides[:-2], x.strides[-1], x.strides[-2]))
+
+
+def gesvj_device(env, x: DeviceArray, job: int, rcond: float = 0.0):
+    """``pthip_gesvj_batched`` on a stack (..., m, n) of the wave tier.  job 0: [S]; 1 / 2: [U, S, Vt] economic / full;
+    3: [pinv].  Leading dimensions reach the kernel as one batch stride where they fold (a broadcast or strided stack
+    included: nothing is copied); the dimensions that do not fold are walked here, one launch per outer index."""
+    from pytensor_amd.dispatch.lu import _batch_strides, _collapse_batch
+
+    *lead, m, n = x.shape
+    lead = tuple(lead)
+    k, dt = min(m, n), x.dtype
+    if job == 3:
+        outs = [DeviceArray.empty((*lead, n, m), dt)]
+        slots = [None, None, None, outs[0]]
+    else:
+        S = DeviceArray.empty((*lead, k), dt)
+        U = DeviceArray.empty((*lead, m, m if job == 2 else k), dt) if job else None
+        Vt = DeviceArray.empty((*lead, n if job == 2 else k, n), dt) if job else None
+        outs = [U, S, Vt] if job else [S]
+        slots = [U, S, Vt, None]
+    per = [0 if o is None else int(np.prod(o.shape[len(lead):])) * o.itemsize for o in slots]
+    outer, inner, st = _collapse_batch(lead, _batch_strides(x, 2, lead))
+    for f, idx in enumerate(np.ndindex(*[s for s, _ in outer])):
+        off = sum(i * sts[0] for i, (_, sts) in zip(idx, outer))
+        ptrs = [None if o is None else o.ptr + f * inner * p for o, p in zip(slots, per)]
+        ffi.check(env.lib.pthip_gesvj_batched(_dt(x), inner, m, n, job, x.ptr + off * x.itemsize, st[0], x.strides[-2], x.strides[-1],
+                                              float(rcond), *ptrs))
+    return outs
+
+
+def _svd_stack(env, x: DeviceArray, full_matrices: bool, compute_uv: bool):
+    """``svd_device`` of a stack (..., m, n): the wave tier in one launch; above it the kernels of the single matrix,
+    each launched once over the whole stack (transposed copy, svd_rows, transposed copy, geqrf, orgqr, fill_null_rows,
+    a transposed copy of the result) — a launch count that does not depend on the batch."""
+    *lead, m, n = x.shape
+    nb = int(np.prod(lead)) if lead else 1
+    k, dt = min(m, n), x.dtype
+    if nb == 0 or k == 0:
+        S = DeviceArray.empty((*lead, k), dt)
+        if not compute_uv:
+            return [S]
+        um, vn = (m, n) if full_matrices else (k, k)
+        # (k = 0 with full_matrices: the identities np.linalg.svd returns)
+        eye = lambda s: env.to_device(HostValue(np.ascontiguousarray(np.broadcast_to(np.eye(s, dtype=dt), (*lead, s, s)))))
+        U = eye(m) if (full_matrices and nb and m) else DeviceArray.empty((*lead, m, um), dt)
+        Vt = eye(n) if (full_matrices and nb and n) else DeviceArray.empty((*lead, vn, n), dt)
+        return [U, S, Vt]
+    tier = svd_tier(m, n, nb)
+    if tier == "wave":
+        return gesvj_device(env, x, (2 if full_matrices else 1) if compute_uv else 0)
+    if tier is None:
+        raise NotImplementedError(f"hip linker: SVD with min(m, n) = {k} (device tiers: max(m, n) <= {SVD_WAVE_MAX} in one "
+                                  f"launch, min(m, n) <= {SVD_ROWS_MAX} by rows)")
+    tall = m >= n
+    X = (_tb(x) if tall else x).contiguous_copy()  # (..., r, c), r <= c
+    r, c = X.shape[-2:]
+    S = DeviceArray.empty((*lead, r), dt)
+    work = DeviceArray.empty((nb, r, r), dt) if compute_uv else DeviceArray.empty((1,), dt)
+    Wt = DeviceArray.empty((*lead, r, c), dt) if compute_uv else work
+    Pt = DeviceArray.empty((*lead, r, r), dt) if compute_uv else work
+    ffi.check(env.lib.pthip_svd_rows(_dt(x), nb, r, c, int(compute_uv), X.ptr, work.ptr, S.ptr, Wt.ptr, Pt.ptr))
+    env.keepalive.extend((X, work))
+    if not compute_uv:
+        return [S]
+    rows = c if full_matrices else r
+    qr, tau = geqrf_device(env, _tb(Wt))
+    Q = orgqr_device(env, qr, tau, rows)
+    if rows == r:
+        big = Wt
+    else:
+        big = DeviceArray.empty((*lead, rows, c), dt)
+        copy_into(big.view((*lead, r, c), big.strides), Wt)
+    ffi.check(env.lib.pthip_fill_null_rows(_dt(x), nb, rows, c, big.ptr, S.ptr, r, Q.ptr, rows))
+    env.keepalive.extend((Q, qr, tau))
+    if tall:  # x^T = P S Wt  ->  x = Wt^T S P^T
+        return [_tb(big).contiguous(), S, Pt]
+    return [_tb(Pt).contiguous(), S, big]
+
+
+def _stack_operand(env, v, what):
+    from pytensor_amd.dispatch.linalg import _lapack_operands
+
+    (x,) = _lapack_operands(env, what, v)
+    if x.ndim < 2:
+        raise np.linalg.LinAlgError(f"{what}: {x.ndim}-dimensional array given. Array must be at least two-dimensional")
+    return x
+
+
+def svd_stack_op(node, inputs, env):
+    """``Blockwise(SVD)``: the whole stack in one call"""
+    x = _stack_operand(env, inputs[0], "SVD")
+    return svd_device(env, x, bool(node.params["full_matrices"]), bool(node.params["compute_uv"]))
+
+
+def pinv_stack_op(node, inputs, env):
+    """``Blockwise(MatrixPinv)``: job 3 of the wave tier in one launch; above it the batched SVD, the cut-off as one
+    elementwise launch and two batched GEMMs"""
+    x = _stack_operand(env, inputs[0], "MatrixPinv")
+    *lead, m, n = x.shape
+    nb = int(np.prod(lead)) if lead else 1
+    if nb == 0 or m == 0 or n == 0:
+        return [DeviceArray.empty((*lead, n, m), x.dtype)]
+    if x.ndim == 2 or svd_tier(m, n, nb) != "wave":
+        U, S, Vt = svd_device(env, x, False, True)
+        rcond = env.to_device(HostValue(np.asarray([PINV_RCOND], dtype=x.dtype)))
+        if x.ndim == 2:
+            return [_pinv_apply(env, U, S, Vt, rcond)]
+        return [_pinv_apply_stack(env, U, S, Vt, rcond)]
+    return gesvj_device(env, x, 3, PINV_RCOND)
+
+
+def _pinv_apply_stack(env, U, S, Vt, rcond_dev):
+    """``_pinv_apply`` for a stack: U (..., m, k), S (..., k), Vt (..., k, n) -> (..., n, m); three launches whatever
+    the batch"""
+    from pytensor_amd.dispatch.blas import gemm_device
+    from pytensor_amd.dispatch.elemwise import launch_elemwise
+
+    *lead, m, k = U.shape
+    n = Vt.shape[-1]
+    nb = int(np.prod(lead)) if lead else 1
+    dt = str(S.dtype)
+    U, S, Vt = (_reshape(a, (nb, *a.shape[len(lead):])) for a in (U, S, Vt))
+    body = {"in_dtypes": [dt, dt, dt], "out_dtypes": [dt],
+            "body": [{"op": "Mul", "in": [["i", 1], ["i", 2]], "dtype": dt},
+                     {"op": "GT", "in": [["i", 0], ["t", 0]], "dtype": "bool"},
+                     {"op": "Reciprocal", "in": [["i", 0]], "dtype": dt},
+                     {"op": "Switch", "in": [["t", 1], ["t", 2], ["c", 0.0, dt]], "dtype": dt}],
+            "outs": [["t", 3]]}
+    (sinv,), _, _ = launch_elemwise(body, [S, S.view((nb, k), (k, 0)), rcond_dev.view((nb, k), (0, 0))], (nb, k), [dt], None, env)
+    scale = {"in_dtypes": [dt, dt], "out_dtypes": [dt], "body": [{"op": "Mul", "in": [["i", 0], ["i", 1]], "dtype": dt}], "outs": [["t", 0]]}
+    Ut = U.view((nb, k, m), (m * k, 1, k))
+    (scaled,), _, _ = launch_elemwise(scale, [Ut, sinv.view((nb, k, m), (k, 1, 0))], (nb, k, m), [dt], None, env)
+    out = gemm_device(env, 1.0, Vt.view((nb, n, k), (k * n, 1, n)), scaled, batch=True)
+    return out.view((*lead, n, m), _cs((*lead, n, m)))
 
 
 @handler("SVD")

@@ -193,10 +193,14 @@ def blockwise(node, inputs, env):
         from pytensor_amd.dispatch import lu
 
         return lu.eigh(type("_N", (), {"params": cp}), ins, env)
-    if p["core_op"] == "QR" and cp.get("pivoting"):  # (geqp3, orgqr and triu each take the whole stack in one launch)
+    if p["core_op"] == "QR":  # (geqrf / geqp3, orgqr and triu each take the whole stack in one launch)
         from pytensor_amd.dispatch import decomp
 
         return decomp.qr_op(type("_N", (), {"params": cp}), ins, env)
+    if p["core_op"] in ("SVD", "MatrixPinv"):  # (one launch up to max(m, n) = 64, batched kernels above: decomp.svd_tier)
+        from pytensor_amd.dispatch import decomp
+
+        return (decomp.svd_stack_op if p["core_op"] == "SVD" else decomp.pinv_stack_op)(type("_N", (), {"params": cp}), ins, env)
     if p["core_op"] == "SolveDiscreteARE":  # (one launch for the whole batch up to m = 64)
         from pytensor_amd.dispatch import riccati
 

@@ -139,6 +139,7 @@ SIGNATURES = {
     "pthip_orgqr": (_int, [_int, _i64, _i64, _i64, _i64, _vp, _i64, _i64, _vp, _vp]),
     "pthip_svd_rows": (_int, [_int, _i64, _i64, _i64, _int, _vp, _vp, _vp, _vp, _vp]),
     "pthip_fill_null_rows": (_int, [_int, _i64, _i64, _i64, _vp, _vp, _i64, _vp, _i64]),
+    "pthip_gesvj_batched": (_int, [_int, _i64, _i64, _i64, _int, _vp, _i64, _i64, _i64, _dbl, _vp, _vp, _vp, _vp]),
     "pthip_triu": (_int, [_int, _i64, _i64, _i64, _vp, _i64, _i64, _vp, _int, _int]),
     "pthip_gttrf": (_int, [_int, _i64, _i64, _vp, _vp, _vp, _vp, _vp]),
     "pthip_gttrs": (_int, [_int, _i64, _i64, _i64, _int, _vp, _vp, _vp, _vp, _vp, _vp]),
