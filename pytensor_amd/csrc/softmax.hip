@@ -27,7 +27,10 @@ template <> __device__ __forceinline__ double dev_exp(double x) { return exp(x);
 template <> __device__ __forceinline__ float dev_exp(float x) { return expf(x); }
 template <class T> __device__ __forceinline__ T dev_log(T x);
 template <> __device__ __forceinline__ double dev_log(double x) { return log(x); }
-template <> __device__ __forceinline__ float dev_log(float x) { return logf(x); }
+// log of a row's sum, once per row, subtracted from every element of a float32 log-softmax: logf's error (log2 to 1 ulp,
+// scaled by ln 2) would land on every element of the row, so the log is taken in double and rounded once, as the
+// log-sum-exp kernels below do (`(T)log(s)`).
+template <> __device__ __forceinline__ float dev_log(float x) { return (float)log((double)x); }
 
 // NaN-propagating max like the reference's Maximum (scalar/basic.py:1744)
 template <class T> __device__ __forceinline__ T nan_max(T a, T b) {
@@ -711,7 +714,11 @@ __global__ __launch_bounds__(BLOCK) void col_softmax_norm_kernel(T* __restrict__
   for (int e = 0; e < V; e++) {
     sh[e] = (T)fm[b * g.C + col + e];
     const double ss = fs[b * g.C + col + e];
-    k[e] = LOG ? (T)log(ss) : (T)(1.0 / (double)(T)ss);  // (the reference divides by the sum rounded to T)
+    const T st = (T)ss;  // (the reference divides by the sum rounded to T)
+    // A column with a +inf entry has shift 0 and an infinite sum.  1 / inf = 0 would turn its finite entries into
+    // exp(x) * 0 = 0; the reference's exp(x - max) / sum has inf - inf = NaN in the sum and gives NaN for the whole
+    // slice, as the row kernels above do.  (The LOG form is (x - 0) - inf = -inf there, NaN at the +inf entry.)
+    k[e] = LOG ? (T)log(ss) : (__builtin_isinf(st) ? (T)__builtin_nan("") : (T)(1.0 / (double)st));
   }
   const long long step = (long long)g.TY * g.C;
   const long long off = (b * g.R) * g.C + col;

@@ -108,6 +108,7 @@ def test_non_finite_entries_follow_the_reference(hip):
         sm, smw = _cols(hip, x, "softmax"), sp.softmax(x, axis=1)
     np.testing.assert_allclose(sm[0][:, [0, 4, 5]], smw[0][:, [0, 4, 5]], rtol=1e-12)
     assert np.isnan(sm[0][:, 1]).all() and np.isnan(sm[0][:, 3]).all()  # 0/0 and NaN, as exp(x - 0) / 0 in the reference
+    assert np.isnan(smw[0][:, 2]).all() and np.isnan(sm[0][:, 2]).all()  # a +inf entry: inf - inf in the sum, not exp(x) * (1 / inf) = 0
     rows = np.random.default_rng(7).normal(size=(300, 9))
     rows[5] = -np.inf
     rows[6, 2] = np.inf
