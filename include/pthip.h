@@ -359,6 +359,19 @@ int pthip_orgqr(int dtype, int64_t batch, int64_t m, int64_t ncols, int64_t k, c
  * Pt_work: r x r scratch.  Non-convergence (60 sweeps) raises bit 2 of the device error word. */
 int pthip_svd_rows(int dtype, int64_t batch, int64_t r, int64_t c, int vectors, void* X, void* Pt_work, void* S,
                    void* Wt, void* Pt);
+/* The whole-chip tier of the same factorisation (csrc/eigh.hip, beside the block Eigh it is built from): block
+ * one-sided Jacobi on the rows of X (batch x r x c contiguous, r <= c, any r >= 1; read, not destroyed):
+ * X = Pt^T diag(S) Wt[:r], S (batch x r) descending, ties by position.  vectors != 0: Pt (batch x r x r) and Wt
+ * (batch x rows_out x c) with rows_out = r (economic) or c (full matrices); the rows of Wt that belong to a singular
+ * value 0, and the rows r.. of the full form, are an orthonormal completion computed in the call.  vectors == 0: Wt and
+ * Pt are not touched and may be NULL.  float32 / float64.  The items of a batch are walked inside the call.  An item
+ * holding a NaN or an Inf is all NaN in every output and raises bit 2 of the device error word, as running into the
+ * sweep cap (60) does.  The call reads the device once per sweep: inside a stream capture it is refused (an error
+ * return) before it touches the stream. */
+int pthip_svd_block(int dtype, int64_t batch, int64_t r, int64_t c, int vectors, int64_t rows_out, const void* X, void* S,
+                    void* Wt, void* Pt);
+/* outer sweeps the last item of the last pthip_svd_block call took (0: non-finite input) */
+int pthip_svd_block_sweeps(void);
 /* rows i of Wt (r x c) with i >= r_valid or S[i] == 0 (S: r_valid per item) are replaced by column
  * i of Q (c x ldq): an orthonormal completion of a rank-deficient or economy-sized factor */
 int pthip_fill_null_rows(int dtype, int64_t batch, int64_t r, int64_t c, void* Wt, const void* S, int64_t r_valid,

@@ -46,7 +46,7 @@ __global__ __launch_bounds__(BLOCK) void eigh_jacobi_kernel(const T* __restrict_
                                                            T* __restrict__ Vout, int n, int lower, int a_lds,
                                                            int v_lds, T* scratchA, T* scratchV,
                                                            int* __restrict__ status, int sorted, int max_sweeps,
-                                                           int cross) {
+                                                           int cross, int rel_only) {
   extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
   __shared__ T s_c[MAX_N / 2], s_s[MAX_N / 2];
   __shared__ short s_p[MAX_N / 2], s_q[MAX_N / 2], s_rank[MAX_N];
@@ -77,8 +77,9 @@ __global__ __launch_bounds__(BLOCK) void eigh_jacobi_kernel(const T* __restrict_
   __syncthreads();
   fro = T(0);
   for (int w = 0; w < BLOCK / 64; w++) fro += s_red[w];
-  // below this, a rotation changes nothing at working precision relative to ||A||
-  const T tiny_abs = Eps<T>::v * T(1.0 / 1024) * sqrt(fro);
+  // below this, a rotation changes nothing at working precision relative to ||A||.  rel_only (the Gram matrices of the
+  // block SVD below, whose small rows must still be orthogonalised against each other): the relative test alone
+  const T tiny_abs = rel_only ? T(0) : Eps<T>::v * T(1.0 / 1024) * sqrt(fro);
 
   const int m = (n + 1) & ~1, half = m >> 1;
   bool converged = n < 2;
@@ -613,15 +614,19 @@ __global__ __launch_bounds__(256) void eigh_scatter_kernel(const T* __restrict__
 // round's pairing wants it (dst_row: the tournament step as a scatter) — what were two batched GEMMs (13 us each for
 // 64 x N x 64 products) and two row gathers.  grid (N / 64 column chunks, pairs, 2); a workgroup holds U_p and a
 // 64 x 64 chunk of the rows in LDS, a thread accumulates a 4 x 4 piece of the result over the 64 terms in index order.
+// The two matrices have row lengths of their own, NG and NV, both multiples of 64 (Eigh: both N; the block SVD below:
+// the padded row length of X and the row count); grid.x covers the longer one, grid.z = 1 leaves Vt out.
 template <class T>
 __global__ __launch_bounds__(256) void eigh_pair_update_kernel(const T* __restrict__ U, const T* __restrict__ Gt, const T* __restrict__ Vt,
-                                                               T* __restrict__ Gout, T* __restrict__ Vout, long long N,
+                                                               T* __restrict__ Gout, T* __restrict__ Vout, long long NG, long long NV,
                                                                const long long* __restrict__ dst_row) {
   constexpr int M = 2 * EB;  // 64
   __shared__ __attribute__((aligned(16))) T Us[M][M];  // U[i][i']
   __shared__ __attribute__((aligned(16))) T Xs[M][M];  // X[i][c]
   const int tid = threadIdx.x;
   const long long c0 = (long long)blockIdx.x * M, p = blockIdx.y;
+  const long long N = blockIdx.z ? NV : NG;
+  if (c0 >= N) return;
   const T* X = (blockIdx.z ? Vt : Gt) + p * M * N + c0;
   T* Y = blockIdx.z ? Vout : Gout;
   const T* Up = U + p * M * M;
@@ -659,7 +664,37 @@ __global__ void eigh_status_or_kernel(int* status, int bits) { atomicOr(status, 
 
 template <class T>
 int eigh_typed(long long batch, long long n, int lower, const void* A, void* W, void* V, int sorted = 1, int max_sweeps = MAX_SWEEPS,
-               int cross = 0);
+               int cross = 0, int rel_only = 0);
+
+// the tournament step on block positions (pairs are the adjacent positions 2k, 2k+1): position 0 stays, the top
+// row shifts right, the bottom row shifts left.  As a row gather (idx, may be null): new row r of block position q comes
+// from row idx[r]; the same step as a scatter (dst): row r of a round's result goes to row dst[r].  Both are uploaded
+// (N = 2 EB npairs entries each) and the stream is synchronised: the host tables go out of scope here.
+int eigh_tournament_upload(long long npairs, long long* idx, long long* dst, hipStream_t st) {
+  const long long nbk = 2 * npairs, N = nbk * EB;
+  std::vector<long long> src(nbk), h(N);
+  const long long hp = npairs;
+  for (long long k = 0; k < hp; k++) {
+    // top_k = position 2k, bottom_k = position 2k+1
+    long long top_src, bot_src;
+    if (k == 0) top_src = 0;
+    else if (k == 1) top_src = 1;                 // bottom_0
+    else top_src = 2 * (k - 1);                    // top_{k-1}
+    if (k == hp - 1) bot_src = hp == 1 ? 1 : 2 * (hp - 1);  // top_{hp-1}
+    else bot_src = 2 * (k + 1) + 1;                // bottom_{k+1}
+    src[2 * k] = top_src;
+    src[2 * k + 1] = bot_src;
+  }
+  for (long long q = 0; q < nbk; q++)
+    for (long long t = 0; t < EB; t++) h[q * EB + t] = src[q] * EB + t;
+  if (idx != nullptr)
+    if (hipError_t e = hipMemcpyAsync(idx, h.data(), (size_t)N * 8, hipMemcpyHostToDevice, st); e != hipSuccess) return pthip::check(e, "eigh idx upload");
+  std::vector<long long> inv(N);
+  for (long long r_ = 0; r_ < N; r_++) inv[nbk > 2 ? h[r_] : r_] = r_;  // (one pair: nothing moves)
+  if (hipError_t e = hipMemcpyAsync(dst, inv.data(), (size_t)N * 8, hipMemcpyHostToDevice, st); e != hipSuccess) return pthip::check(e, "eigh dst upload");
+  if (hipError_t e = hipStreamSynchronize(st); e != hipSuccess) return pthip::check(e, "eigh idx sync");
+  return 0;
+}
 
 template <class T>
 int eigh_block_jacobi(long long n, int lower, const T* A, T* W, T* V) {
@@ -685,36 +720,13 @@ int eigh_block_jacobi(long long n, int lower, const T* A, T* W, T* V) {
   T* U = (T*)p; p += sbytes;
   T* Wsub = (T*)p; p += ((size_t)npairs * m * sizeof(T) + 255) / 256 * 256;
   long long* idx = (long long*)p; p += ibytes;
-  long long* dst = (long long*)p; p += ibytes;  // the same step as a scatter: row r of a round's result goes to row dst[r]
+  long long* dst = (long long*)p; p += ibytes;
   int* rank = (int*)p; p += ibytes;
   T* lam = (T*)p; p += lbytes;
   unsigned long long* maxbits = (unsigned long long*)p;  // [0] ||A||_inf bits, [1] low word: off-diagonal bits, [2] ||A^4||_inf bits
   unsigned* offbits = (unsigned*)(maxbits + 1);
   T* sigma = (T*)(maxbits + 3);
-  // the tournament step on block positions (pairs are the adjacent positions 2k, 2k+1): position 0 stays, the top
-  // row shifts right, the bottom row shifts left; as a row gather: new row r of block position q comes from ...
-  {
-    std::vector<long long> src(nbk), h(N);
-    const long long hp = npairs;
-    for (long long k = 0; k < hp; k++) {
-      // top_k = position 2k, bottom_k = position 2k+1
-      long long top_src, bot_src;
-      if (k == 0) top_src = 0;
-      else if (k == 1) top_src = 1;                 // bottom_0
-      else top_src = 2 * (k - 1);                    // top_{k-1}
-      if (k == hp - 1) bot_src = hp == 1 ? 1 : 2 * (hp - 1);  // top_{hp-1}
-      else bot_src = 2 * (k + 1) + 1;                // bottom_{k+1}
-      src[2 * k] = top_src;
-      src[2 * k + 1] = bot_src;
-    }
-    for (long long q = 0; q < nbk; q++)
-      for (long long t = 0; t < EB; t++) h[q * EB + t] = src[q] * EB + t;
-    if (hipError_t e = hipMemcpyAsync(idx, h.data(), (size_t)N * 8, hipMemcpyHostToDevice, st); e != hipSuccess) return fail(pthip::check(e, "eigh idx upload"));
-    std::vector<long long> inv(N);
-    for (long long r_ = 0; r_ < N; r_++) inv[nbk > 2 ? h[r_] : r_] = r_;  // (one pair: nothing moves)
-    if (hipError_t e = hipMemcpyAsync(dst, inv.data(), (size_t)N * 8, hipMemcpyHostToDevice, st); e != hipSuccess) return fail(pthip::check(e, "eigh dst upload"));
-    if (hipError_t e = hipStreamSynchronize(st); e != hipSuccess) return fail(pthip::check(e, "eigh idx sync"));  // (h goes out of scope)
-  }
+  if ((r = eigh_tournament_upload(npairs, idx, dst, st))) return fail(r);
   if (hipError_t e = hipMemsetAsync(maxbits, 0, 32, st); e != hipSuccess) return fail(pthip::check(e, "eigh memset"));
   PTHIP_KLAUNCH((eigh_rowsum_kernel<T>), dim3((unsigned)((n + 3) / 4)), dim3(256), 0, st, A, n, lower, maxbits);
   const unsigned pg = (unsigned)(N * N / 256 > 4096 ? 4096 : (N * N + 255) / 256);
@@ -762,7 +774,7 @@ int eigh_block_jacobi(long long n, int lower, const T* A, T* W, T* V) {
       static const bool fused_update = !(getenv("PTHIP_EIGH_FUSED_UPDATE") && atoi(getenv("PTHIP_EIGH_FUSED_UPDATE")) == 0);
       if (fused_update) {
         PTHIP_KLAUNCH((eigh_pair_update_kernel<T>), dim3((unsigned)(N / m), (unsigned)npairs, 2u), dim3(256), 0, st, (const T*)U, (const T*)Gt,
-                      (const T*)Vt, G2, V2, N, (const long long*)dst);
+                      (const T*)Vt, G2, V2, N, N, (const long long*)dst);
         std::swap(Gt, G2);
         std::swap(Vt, V2);
         continue;
@@ -803,7 +815,8 @@ int eigh_block_jacobi(long long n, int lower, const T* A, T* W, T* V) {
 }
 
 template <class T>
-int eigh_typed(long long batch, long long n, int lower, const void* A, void* W, void* V, int sorted, int max_sweeps, int cross) {
+int eigh_typed(long long batch, long long n, int lower, const void* A, void* W, void* V, int sorted, int max_sweeps, int cross,
+               int rel_only) {
   if (batch == 0 || n == 0) return 0;
   static const bool no_block = getenv("PTHIP_EIGH_ONE_WG") != nullptr;
   if (n > EIGH_BLOCK_MIN && !(no_block && n <= MAX_N)) {
@@ -845,14 +858,323 @@ int eigh_typed(long long batch, long long n, int lower, const void* A, void* W, 
   if (!a_lds) { int r = pthip_alloc((size_t)batch * one, &sa); if (r) return r; }
   if (!v_lds) { int r = pthip_alloc((size_t)batch * one, &sv); if (r) { if (sa) pthip_free(sa); return r; } }
   PTHIP_KLAUNCH(k, dim3((unsigned)batch), dim3(wide ? 1024 : 256), dyn, st, (const T*)A, (T*)W, (T*)V, (int)n, lower,
-                     a_lds ? 1 : 0, v_lds ? 1 : 0, (T*)sa, (T*)sv, (int*)pthip_status_ptr(), sorted, max_sweeps, (cross && n % 2 == 0) ? 1 : 0);
+                     a_lds ? 1 : 0, v_lds ? 1 : 0, (T*)sa, (T*)sv, (int*)pthip_status_ptr(), sorted, max_sweeps, (cross && n % 2 == 0) ? 1 : 0,
+                     rel_only);
   int r = pthip::post_launch("eigh");
   if (sa) pthip_free(sa);  // stream-ordered reuse keeps this safe
   if (sv) pthip_free(sv);
   return r;
 }
 
+// ------------------------------------------------------------------------------------------
+// The same iteration on the rows of a general matrix: Hestenes' SVD over the whole chip (pthip_svd_block).
+//
+// X (r x c, r <= c) = Pt^T diag(s) Wt.  The rows of X take the place of the columns of G = B V above: a round pairs the
+// 32-row blocks by the same tournament, a pair's 64 x 64 Gram matrix S = X_p X_p^T comes from the same batched GEMM, its
+// rotation matrix U from the same LDS Jacobi kernel (unsorted, one inner sweep, cross pairs after a sweep's first
+// round) and X_p <- U^T X_p, Pt_p <- U^T Pt_p from the same pair-update kernel.  What differs:
+//   - the input is scaled by a power of two so that its largest entry lies in [1, 2) (exact; s is scaled back), which
+//     keeps the Gram matrices far from over- and underflow;
+//   - r is padded to N, a whole number of 64-row pairs, by rows that hold a single 1 in a padding column of their own
+//     (row r + i in column c + i; the row length is rounded up to a multiple of 64, LDC, with zeros): their inner
+//     product with every other row is an exact zero, so they are never rotated, and at the end they are the rows with a
+//     nonzero in a padding column — a real all-zero row is not one of them and comes out as a singular value 0;
+//   - the inner solver runs with its relative threshold alone (rel_only): a general matrix is not conditioned like
+//     the shifted B, and rows whose norms are 1e-10 of the largest still have to be orthogonalised against each other;
+//   - X is not recomputed from Pt and the input between sweeps: that product has an absolute error eps ||X||, which
+//     would undo the relative orthogonality of small rows at every sweep (a graded matrix would never converge);
+//   - s = row norms, ranked descending by counting; rows / s normalised into Wt, Pt scattered in rank order; the rows of
+//     Wt a singular value 0 leaves empty, and rows r.. of the full form, are the eigenvectors of the eigenvalue 1 of the
+//     projector I - Wt^T Wt (eigh_typed above: two exactly separated clusters) — only when there are such rows.
+// One host read per sweep, as above, one before the first (non-finite input, the scale) and one for the count of zeros.
+// ------------------------------------------------------------------------------------------
+// LAPACK's gesvj allows 30 sweeps, on a matrix its QR preconditioning has prepared; the rows of a graded or rank-deficient
+// matrix taken as they are need more (96 x 96 with condition 1e12: 30; rank 40 of 129 x 200: over 30): the cap of the
+// other SVD kernels
+constexpr int SVDB_MAX_SWEEPS = 60;
+
+// largest finite |x| (bits of a non-negative double) and whether any entry is a NaN or an Inf
+template <class T>
+__global__ __launch_bounds__(256) void svdb_absmax_kernel(const T* __restrict__ X, long long total, unsigned long long* __restrict__ maxbits,
+                                                          int* __restrict__ bad) {
+  double best = 0.0;
+  int nf = 0;
+  for (long long e = (long long)blockIdx.x * 256 + threadIdx.x; e < total; e += (long long)gridDim.x * 256) {
+    const double x = (double)X[e];
+    const double a = x < 0.0 ? -x : x;
+    if (!(a <= 1.7976931348623157e308)) nf = 1;
+    else best = a > best ? a : best;
+  }
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) { const double ov = __shfl_xor(best, o); best = ov > best ? ov : best; }
+  if ((threadIdx.x & 63) == 0 && best > 0.0) atomicMax(maxbits, (unsigned long long)__double_as_longlong(best));
+  if (nf) atomicOr(bad, 1);
+}
+
+// X (N x LDC) = scale * input with the padding described above; Pt (N x N, may be null) = I
+template <class T>
+__global__ __launch_bounds__(256) void svdb_prep_kernel(const T* __restrict__ Xin, long long r, long long c, long long N, long long LDC,
+                                                        T scale, T* __restrict__ X, T* __restrict__ Pt) {
+  const long long total = N * LDC;
+  for (long long e = (long long)blockIdx.x * 256 + threadIdx.x; e < total; e += (long long)gridDim.x * 256) {
+    const long long i = e / LDC, j = e - i * LDC;
+    T v = T(0);
+    if (i < r) { if (j < c) v = Xin[i * c + j] * scale; }
+    else if (j == c + (i - r)) v = T(1);
+    X[e] = v;
+  }
+  if (Pt != nullptr) {
+    const long long tp = N * N;
+    for (long long e = (long long)blockIdx.x * 256 + threadIdx.x; e < tp; e += (long long)gridDim.x * 256) {
+      const long long i = e / N, j = e - i * N;
+      Pt[e] = i == j ? T(1) : T(0);
+    }
+  }
+}
+
+// lam_i = |row i of X| over the c real columns, -1 for a padding row (one wave per row)
+template <class T>
+__global__ __launch_bounds__(256) void svdb_norm_kernel(const T* __restrict__ X, long long N, long long LDC, long long c, T* __restrict__ lam) {
+  const int lane = threadIdx.x & 63;
+  const long long i = (long long)blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (i >= N) return;
+  double s = 0.0, pad = 0.0;
+  for (long long j = lane; j < LDC; j += 64) {
+    const double x = (double)X[i * LDC + j];
+    if (j < c) s += x * x;
+    else pad += x * x;
+  }
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) { s += __shfl_xor(s, o); pad += __shfl_xor(pad, o); }
+  if (lane == 0) lam[i] = pad > 0.0 ? T(-1) : (T)sqrt(s);
+}
+
+// descending ranks (ties by position; the padding rows, lam = -1, come last), the r singular values scaled back and
+// written out, the zeros among them counted
+template <class T>
+__global__ __launch_bounds__(256) void svdb_rank_kernel(const T* __restrict__ lam, long long N, long long r, T scale, int* __restrict__ rank,
+                                                        T* __restrict__ S, int* __restrict__ nzero) {
+  const long long j = (long long)blockIdx.x * 256 + threadIdx.x;
+  if (j >= N) return;
+  const T wj = lam[j];
+  int rk = 0;
+  for (long long k = 0; k < N; k++) {
+    const T wk = lam[k];
+    rk += (wk > wj || (wk == wj && k < j)) ? 1 : 0;
+  }
+  rank[j] = rk;
+  if (rk < r) {
+    S[rk] = wj / scale;
+    if (wj == T(0)) atomicAdd(nzero, 1);
+  }
+}
+
+// Wt[rank_j] = row j of X / lam_j (zeros where lam_j is 0), Pout[rank_j] = row j of Pt, for the r real rows
+template <class T>
+__global__ __launch_bounds__(256) void svdb_scatter_kernel(const T* __restrict__ X, const T* __restrict__ Pt, const T* __restrict__ lam,
+                                                           const int* __restrict__ rank, long long N, long long LDC, long long r,
+                                                           long long c, T* __restrict__ Wt, T* __restrict__ Pout) {
+  const long long j = blockIdx.y;
+  const long long rk = rank[j];
+  if (rk >= r) return;
+  const T s = lam[j];
+  for (long long k = (long long)blockIdx.x * 256 + threadIdx.x; k < c; k += (long long)gridDim.x * 256) {
+    Wt[rk * c + k] = s > T(0) ? X[j * LDC + k] / s : T(0);
+    if (k < r) Pout[rk * r + k] = Pt[j * N + k];
+  }
+}
+
+template <class T>
+__global__ __launch_bounds__(256) void svdb_fill_kernel(T* __restrict__ out, long long total, T value) {
+  for (long long e = (long long)blockIdx.x * 256 + threadIdx.x; e < total; e += (long long)gridDim.x * 256) out[e] = value;
+}
+
+template <class T>
+__global__ __launch_bounds__(256) void svdb_eye_kernel(T* __restrict__ out, long long n) {
+  for (long long e = (long long)blockIdx.x * 256 + threadIdx.x; e < n * n; e += (long long)gridDim.x * 256) out[e] = (e / n == e % n) ? T(1) : T(0);
+}
+
+// rows first .. first + count - 1 of Wt (c long) = the last `count` columns of V (c x c)
+template <class T>
+__global__ __launch_bounds__(256) void svdb_complete_kernel(const T* __restrict__ V, long long c, long long first, long long count,
+                                                            T* __restrict__ Wt) {
+  const long long total = count * c;
+  for (long long e = (long long)blockIdx.x * 256 + threadIdx.x; e < total; e += (long long)gridDim.x * 256) {
+    const long long t = e / c, i = e - t * c;
+    Wt[(first + t) * c + i] = V[i * c + (c - count + t)];
+  }
+}
+
+inline unsigned svdb_grid(long long total) { return (unsigned)(total / 256 >= 4096 ? 4096 : (total + 255) / 256); }
+
+int svdb_last_sweeps = 0;  // sweeps of the last item (pthip_svd_block_sweeps: the benchmark records them)
+
+// the missing rows of Wt (rows_out x c; rows 0 .. kv-1 are orthonormal): rows kv .. rows_out-1
+template <class T>
+int svd_block_complete(long long c, long long kv, long long rows_out, T* Wt) {
+  hipStream_t st = pthip::ctx().stream;
+  const int dt = sizeof(T) == 8 ? PTHIP_F64 : PTHIP_F32;
+  const size_t mat = ((size_t)c * c * sizeof(T) + 255) / 256 * 256;
+  void* ws = nullptr;
+  int r = pthip_alloc(3 * mat + (size_t)c * sizeof(T), &ws);
+  if (r) return r;
+  auto fail = [&](int rc) { pthip_free(ws); return rc; };
+  T* Eye = (T*)ws;
+  T* Cm = (T*)((char*)ws + mat);
+  T* V = (T*)((char*)ws + 2 * mat);
+  T* W = (T*)((char*)ws + 3 * mat);
+  PTHIP_KLAUNCH((svdb_eye_kernel<T>), dim3(svdb_grid(c * c)), dim3(256), 0, st, kv > 0 ? Eye : Cm, c);
+  if ((r = pthip::post_launch("svd_block_eye"))) return fail(r);
+  // C = I - Wt^T Wt over the valid rows: an orthogonal projector, eigenvalue 0 (kv times) and 1
+  if (kv > 0)
+    if ((r = pthip_gemm(dt, 1, c, c, kv, -1.0, Wt, 0, 1, c, Wt, 0, c, 1, 1.0, Eye, 0, c, 1, Cm))) return fail(r);
+  if ((r = eigh_typed<T>(1, c, 1, Cm, W, V))) return fail(r);
+  const long long count = rows_out - kv;
+  PTHIP_KLAUNCH((svdb_complete_kernel<T>), dim3(svdb_grid(count * c)), dim3(256), 0, st, (const T*)V, c, kv, count, Wt);
+  r = pthip::post_launch("svd_block_complete");
+  pthip_free(ws);
+  return r;
+}
+
+template <class T>
+int svd_block_item(long long r, long long c, int vectors, long long rows_out, const T* Xin, T* S, T* Wt, T* Pout) {
+  hipStream_t st = pthip::ctx().stream;
+  const int dt = sizeof(T) == 8 ? PTHIP_F64 : PTHIP_F32;
+  const long long m = 2 * EB;
+  const long long npairs = (r + m - 1) / m, N = npairs * m, nbk = 2 * npairs;
+  const long long LDC = (c + (N - r) + m - 1) / m * m;
+  const size_t xbytes = (size_t)N * LDC * sizeof(T), pbytes = vectors ? (size_t)N * N * sizeof(T) : 0;
+  const size_t sbytes = (size_t)npairs * m * m * sizeof(T);
+  const size_t ibytes = ((size_t)N * 8 + 255) / 256 * 256;
+  void* ws = nullptr;
+  int rc = pthip_alloc(2 * xbytes + 2 * pbytes + 2 * sbytes + 4 * ibytes + 256, &ws);
+  if (rc) return rc;
+  auto fail = [&](int e) { pthip_free(ws); return e; };
+  char* p = (char*)ws;
+  T* X = (T*)p; p += xbytes;
+  T* X2 = (T*)p; p += xbytes;
+  T* Pt = vectors ? (T*)p : nullptr; p += pbytes;
+  T* P2 = vectors ? (T*)p : nullptr; p += pbytes;
+  T* Sg = (T*)p; p += sbytes;
+  T* U = (T*)p; p += sbytes;
+  T* Wsub = (T*)p; p += ibytes;
+  long long* dst = (long long*)p; p += ibytes;
+  int* rank = (int*)p; p += ibytes;
+  T* lam = (T*)p; p += ibytes;
+  unsigned long long* maxbits = (unsigned long long*)p;  // [0] max |x| bits; then three words: off-diagonal bits, non-finite flag, zeros
+  unsigned* offbits = (unsigned*)(maxbits + 1);
+  int* bad = (int*)(offbits + 1);
+  int* nzero = bad + 1;
+  svdb_last_sweeps = 0;
+  if (hipError_t e = hipMemsetAsync(maxbits, 0, 32, st); e != hipSuccess) return fail(pthip::check(e, "svd_block memset"));
+  PTHIP_KLAUNCH((svdb_absmax_kernel<T>), dim3(svdb_grid(r * c)), dim3(256), 0, st, Xin, r * c, maxbits, bad);
+  if ((rc = pthip::post_launch("svd_block_absmax"))) return fail(rc);
+  unsigned long long head[2] = {0, 0};
+  if (hipError_t e = hipMemcpyAsync(head, maxbits, 16, hipMemcpyDeviceToHost, st); e != hipSuccess) return fail(pthip::check(e, "svd_block scale read"));
+  if (hipError_t e = hipStreamSynchronize(st); e != hipSuccess) return fail(pthip::check(e, "svd_block scale sync"));
+  int hbad;
+  memcpy(&hbad, (char*)head + 12, 4);
+  if (hbad) {
+    // np.linalg.svd raises LinAlgError("SVD did not converge") for such input: all NaN, bit 2, no sweep
+    T nan;
+    if constexpr (sizeof(T) == 8) nan = __builtin_nan(""); else nan = __builtin_nanf("");
+    PTHIP_KLAUNCH((svdb_fill_kernel<T>), dim3(svdb_grid(r)), dim3(256), 0, st, S, r, nan);
+    if (vectors) {
+      PTHIP_KLAUNCH((svdb_fill_kernel<T>), dim3(svdb_grid(rows_out * c)), dim3(256), 0, st, Wt, rows_out * c, nan);
+      PTHIP_KLAUNCH((svdb_fill_kernel<T>), dim3(svdb_grid(r * r)), dim3(256), 0, st, Pout, r * r, nan);
+    }
+    PTHIP_KLAUNCH(eigh_status_or_kernel, dim3(1), dim3(1), 0, st, (int*)pthip_status_ptr(), 4);
+    rc = pthip::post_launch("svd_block_nonfinite");
+    pthip_free(ws);
+    return rc;
+  }
+  double amax;
+  memcpy(&amax, head, 8);
+  int ex = 1;
+  if (amax > 0.0) frexp(amax, &ex);  // amax = f 2^ex, f in [0.5, 1): amax 2^(1 - ex) in [1, 2)
+  const int elim = sizeof(T) == 8 ? 1000 : 120;  // (the scale itself must be a normal number of T)
+  const int sh = 1 - ex > elim ? elim : (1 - ex < -elim ? -elim : 1 - ex);
+  const T scale = (T)ldexp(1.0, sh);
+  if ((rc = eigh_tournament_upload(npairs, nullptr, dst, st))) return fail(rc);
+  PTHIP_KLAUNCH((svdb_prep_kernel<T>), dim3(svdb_grid(N * (LDC > N ? LDC : N))), dim3(256), 0, st, Xin, r, c, N, LDC, scale, X, Pt);
+  if ((rc = pthip::post_launch("svd_block_prep"))) return fail(rc);
+  const double eps = sizeof(T) == 8 ? 2.220446049250313e-16 : 1.1920929e-07;
+  // the Gram matrices carry a rounding error of order eps sqrt(row length): a threshold of the bare eps would rotate a
+  // pair back and forth for ever (DESIGN §4 "Batched SVD")
+  const double sq = 4.0 * sqrt((double)LDC);
+  const double tol = eps * (sq > 64.0 ? sq : 64.0);
+  double prev = 1e300;
+  bool converged = false;
+  for (int sweep = 0; sweep < SVDB_MAX_SWEEPS && !converged; sweep++) {
+    const long long rounds = nbk > 2 ? nbk - 1 : 1;
+    for (long long rd = 0; rd < rounds; rd++) {
+      if ((rc = pthip_gemm(dt, npairs, m, m, LDC, 1.0, X, m * LDC, LDC, 1, X, m * LDC, 1, LDC, 0.0, nullptr, 0, 0, 0, Sg))) return fail(rc);
+      PTHIP_KLAUNCH((eigh_offdiag_kernel<T>), dim3((unsigned)(npairs * m * m / 256)), dim3(256), 0, st, (const T*)Sg, npairs, (int)m, offbits);
+      // (one inner sweep; cross pairs only after the sweep's first round while far from done: see eigh_block_jacobi)
+      const int cross = (rd > 0 && prev > 1e-3) ? 1 : 0;
+      if ((rc = eigh_typed<T>(npairs, m, 1, Sg, Wsub, U, /*sorted=*/0, /*max_sweeps=*/1, cross, /*rel_only=*/1))) return fail(rc);
+      PTHIP_KLAUNCH((eigh_pair_update_kernel<T>), dim3((unsigned)((LDC > N ? LDC : N) / m), (unsigned)npairs, vectors ? 2u : 1u), dim3(256), 0, st,
+                    (const T*)U, (const T*)X, (const T*)Pt, X2, P2, LDC, N, (const long long*)dst);
+      std::swap(X, X2);
+      std::swap(Pt, P2);
+    }
+    unsigned hb = 0;
+    if (hipError_t e = hipMemcpyAsync(&hb, offbits, 4, hipMemcpyDeviceToHost, st); e != hipSuccess) return fail(pthip::check(e, "svd_block off-diagonal read"));
+    if (hipError_t e = hipStreamSynchronize(st); e != hipSuccess) return fail(pthip::check(e, "svd_block sweep sync"));
+    if (hipError_t e = hipMemsetAsync(offbits, 0, 4, st); e != hipSuccess) return fail(pthip::check(e, "svd_block memset"));
+    float offf;
+    memcpy(&offf, &hb, 4);
+    const double off = offf;
+    svdb_last_sweeps = sweep + 1;
+    converged = off <= tol || (sweep >= 2 && off <= 100 * tol && off > 0.5 * prev);
+    prev = off;
+  }
+  if (!converged) PTHIP_KLAUNCH(eigh_status_or_kernel, dim3(1), dim3(1), 0, st, (int*)pthip_status_ptr(), 4);  // bit 2: "SVD did not converge"
+  PTHIP_KLAUNCH((svdb_norm_kernel<T>), dim3((unsigned)((N + 3) / 4)), dim3(256), 0, st, (const T*)X, N, LDC, c, lam);
+  PTHIP_KLAUNCH((svdb_rank_kernel<T>), dim3((unsigned)((N + 255) / 256)), dim3(256), 0, st, (const T*)lam, N, r, scale, rank, S, nzero);
+  if (!vectors) {
+    rc = pthip::post_launch("svd_block_finish");
+    pthip_free(ws);
+    return rc;
+  }
+  PTHIP_KLAUNCH((svdb_scatter_kernel<T>), dim3((unsigned)((c + 255) / 256), (unsigned)N), dim3(256), 0, st, (const T*)X, (const T*)Pt, (const T*)lam,
+                (const int*)rank, N, LDC, r, c, Wt, Pout);
+  if ((rc = pthip::post_launch("svd_block_finish"))) return fail(rc);
+  int hz = 0;
+  if (hipError_t e = hipMemcpyAsync(&hz, nzero, 4, hipMemcpyDeviceToHost, st); e != hipSuccess) return fail(pthip::check(e, "svd_block zero count read"));
+  if (hipError_t e = hipStreamSynchronize(st); e != hipSuccess) return fail(pthip::check(e, "svd_block finish sync"));
+  pthip_free(ws);
+  if (hz < 0 || hz > r) return pthip::set_error("pthip_svd_block: %d zero singular values of %lld", hz, r);
+  if (rows_out > r || hz > 0) return svd_block_complete<T>(c, r - hz, rows_out, Wt);
+  return 0;
+}
+
+template <class T>
+int svd_block_typed(long long batch, long long r, long long c, int vectors, long long rows_out, const void* X, void* S, void* Wt, void* Pt) {
+  for (long long b = 0; b < batch; b++) {
+    int rc = svd_block_item<T>(r, c, vectors, rows_out, (const T*)X + b * r * c, (T*)S + b * r, vectors ? (T*)Wt + b * rows_out * c : nullptr,
+                               vectors ? (T*)Pt + b * r * r : nullptr);
+    if (rc) return rc;
+  }
+  return 0;
+}
+
 }  // namespace
+
+extern "C" int pthip_svd_block(int dtype, int64_t batch, int64_t r, int64_t c, int vectors, int64_t rows_out, const void* X, void* S,
+                               void* Wt, void* Pt) {
+  PTHIP_REQUIRE_INIT();
+  if (pthip::ctx().capturing) return pthip::set_error("pthip_svd_block: reads the device once per sweep and cannot be captured into a hipGraph");
+  if (batch <= 0 || r <= 0) return 0;
+  if (r > c) return pthip::set_error("pthip_svd_block: %lld rows > %lld columns (pass the transpose)", (long long)r, (long long)c);
+  if (vectors && rows_out != r && rows_out != c)
+    return pthip::set_error("pthip_svd_block: rows_out = %lld is neither r = %lld nor c = %lld", (long long)rows_out, (long long)r, (long long)c);
+  if (dtype == PTHIP_F64) return svd_block_typed<double>(batch, r, c, vectors, rows_out, X, S, Wt, Pt);
+  if (dtype == PTHIP_F32) return svd_block_typed<float>(batch, r, c, vectors, rows_out, X, S, Wt, Pt);
+  return pthip::set_error("pthip_svd_block: dtype %d not supported (float32/float64 only)", dtype);
+}
+
+extern "C" int pthip_svd_block_sweeps(void) { return svdb_last_sweeps; }
 
 // out = the symmetric matrix whose `lower` (or upper) triangle is A's: what LAPACK's sy* routines
 // read.  The generalised problem A v = w B v (Eigh with two inputs, eigen.py:177-186) is reduced on

@@ -8,7 +8,9 @@ solvers/lstsq.py:10 ``Lstsq`` (np.linalg.lstsq), 39 ``TensorSolve``, solvers/tri
 (scipy.linalg.block_diag).  Kernels: csrc/decomp.hip (correct-first tier).
 Leading batch dimensions arrive through ``Blockwise``: ``QR`` (pivoted or not), ``SVD`` and ``MatrixPinv`` take the
 whole stack — ``svd_tier``: one launch of csrc/svd_batched.hip up to max(m, n) = 64, the kernels of the single matrix
-launched once each over the stack above it; dispatch/linalg.py loops the items of the other ops here.
+launched once each over the stack above it, and beyond min(m, n) = 2048 the whole-chip block Jacobi tier
+(``pthip_svd_block``, csrc/eigh.hip), which a single matrix of that size takes as well; dispatch/linalg.py loops the
+items of the other ops here.
 """
 
 from __future__ import annotations
@@ -156,6 +158,8 @@ def svd_device(env, x: DeviceArray, full_matrices: bool, compute_uv: bool):
     if x.ndim > 2:
         return _svd_stack(env, x, full_matrices, compute_uv)
     m, n = x.shape
+    if min(m, n) > SVD_ROWS_MAX:  # (read at call time)
+        return _svd_block(env, x, full_matrices, compute_uv)
     tall = m >= n
     X = (_t(x).contiguous_copy() if tall else x.contiguous_copy())  # r x c, r <= c
     r, c = X.shape
@@ -200,12 +204,40 @@ PINV_RCOND = 1e-15  # np.linalg.pinv's default
 def svd_tier(m: int, n: int, nb: int):
     """The tier that takes a stack of ``nb`` m x n matrices, from the shapes alone: "wave" (one lane group per matrix,
     one launch) up to max(m, n) = 64, "rows" (one ``pthip_svd_rows`` workgroup per matrix, the batch in grid.x, and the
-    batched completion) above that up to min(m, n) = 2048, None (refused) beyond."""
+    batched completion) above that up to min(m, n) = 2048, "block" (``pthip_svd_block``: the whole chip on one matrix
+    at a time, the items walked inside the call) beyond."""
     if max(m, n) <= SVD_WAVE_MAX:
         return "wave"
     if min(m, n) <= SVD_ROWS_MAX:
         return "rows"
-    return None
+    return "block"
+
+
+def _svd_block(env, x: DeviceArray, full_matrices: bool, compute_uv: bool):
+    """``svd_device`` on the block tier, a matrix or a stack (..., m, n) with m, n >= 1: the wide-orientation copy, one
+    ``pthip_svd_block`` call (it completes its own factors) and the factors in ``svd_device``'s layout.  The tier
+    reads the device once per sweep, so it cannot be part of a frozen plan."""
+    if env.exe._capturing:
+        raise ffi.HipError("data-dependent host read inside a frozen (hipGraph) plan")
+    *lead, m, n = x.shape
+    nb = int(np.prod(lead)) if lead else 1
+    tall = m >= n
+    X = (_tb(x) if tall else x).contiguous_copy()  # (..., r, c), r <= c
+    r, c = X.shape[-2:]
+    dt = x.dtype
+    S = DeviceArray.empty((*lead, r), dt)
+    if not compute_uv:
+        ffi.check(env.lib.pthip_svd_block(_dt(x), nb, r, c, 0, r, X.ptr, S.ptr, None, None))
+        env.keepalive.append(X)
+        return [S]
+    rows = c if full_matrices else r
+    Wt = DeviceArray.empty((*lead, rows, c), dt)
+    Pt = DeviceArray.empty((*lead, r, r), dt)
+    ffi.check(env.lib.pthip_svd_block(_dt(x), nb, r, c, 1, rows, X.ptr, S.ptr, Wt.ptr, Pt.ptr))
+    env.keepalive.append(X)
+    if tall:  # x^T = P S Wt  ->  x = Wt^T S P^T
+        return [_tb(Wt).contiguous(), S, Pt]
+    return [_tb(Pt).contiguous(), S, Wt]
 
 
 def _tb(x: DeviceArray) -> DeviceArray:
@@ -261,9 +293,8 @@ def _svd_stack(env, x: DeviceArray, full_matrices: bool, compute_uv: bool):
     tier = svd_tier(m, n, nb)
     if tier == "wave":
         return gesvj_device(env, x, (2 if full_matrices else 1) if compute_uv else 0)
-    if tier is None:
-        raise NotImplementedError(f"hip linker: SVD with min(m, n) = {k} (device tiers: max(m, n) <= {SVD_WAVE_MAX} in one "
-                                  f"launch, min(m, n) <= {SVD_ROWS_MAX} by rows)")
+    if tier == "block":
+        return _svd_block(env, x, full_matrices, compute_uv)
     tall = m >= n
     X = (_tb(x) if tall else x).contiguous_copy()  # (..., r, c), r <= c
     r, c = X.shape[-2:]

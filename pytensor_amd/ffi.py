@@ -138,6 +138,8 @@ SIGNATURES = {
     "pthip_geqp3": (_int, [_int, _i64, _i64, _i64, _vp, _vp, _vp]),
     "pthip_orgqr": (_int, [_int, _i64, _i64, _i64, _i64, _vp, _i64, _i64, _vp, _vp]),
     "pthip_svd_rows": (_int, [_int, _i64, _i64, _i64, _int, _vp, _vp, _vp, _vp, _vp]),
+    "pthip_svd_block": (_int, [_int, _i64, _i64, _i64, _int, _i64, _vp, _vp, _vp, _vp]),
+    "pthip_svd_block_sweeps": (_int, []),
     "pthip_fill_null_rows": (_int, [_int, _i64, _i64, _i64, _vp, _vp, _i64, _vp, _i64]),
     "pthip_gesvj_batched": (_int, [_int, _i64, _i64, _i64, _int, _vp, _i64, _i64, _i64, _dbl, _vp, _vp, _vp, _vp]),
     "pthip_triu": (_int, [_int, _i64, _i64, _i64, _vp, _i64, _i64, _vp, _int, _int]),
