@@ -16,6 +16,7 @@
 //  * SVD: singular values descending; U / V are defined up to a sign per pair (and up to a basis
 //    of the null space / complement), which LAPACK does not fix either.
 #include "common.h"
+#include "wave_device.h"
 
 #include <limits>
 
@@ -23,56 +24,6 @@ namespace {
 
 constexpr int BLOCK = 256;
 constexpr int VMAX = 4096;  // reflector entries staged in LDS (longer ones are read from L2)
-
-template <class T> __device__ __forceinline__ T dabs(T x) { return x < T(0) ? -x : x; }
-
-template <class T> __device__ __forceinline__ T wave_sum(T v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
-  return v;
-}
-
-// the same sum out of DPP row operations and v_readlane (no LDS permutes: __shfl_xor is a ds_bpermute round trip
-// per step, six dependent ones per sum) — used where a wave sum sits on the critical path of every Jacobi rotation
-template <int CTRL> __device__ __forceinline__ double dpp_mov(double v) {
-  return __hiloint2double(__builtin_amdgcn_update_dpp(0, __double2hiint(v), CTRL, 0xf, 0xf, false),
-                          __builtin_amdgcn_update_dpp(0, __double2loint(v), CTRL, 0xf, 0xf, false));
-}
-template <int CTRL> __device__ __forceinline__ float dpp_mov(float v) {
-  return __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), CTRL, 0xf, 0xf, false));
-}
-__device__ __forceinline__ double lane_bcast(double v, int l) {
-  return __hiloint2double(__builtin_amdgcn_readlane(__double2hiint(v), l), __builtin_amdgcn_readlane(__double2loint(v), l));
-}
-__device__ __forceinline__ float lane_bcast(float v, int l) { return __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), l)); }
-template <class T> __device__ __forceinline__ T wave_sum_dpp(T v) {
-  v += dpp_mov<0xB1>(v);   // quad_perm [1,0,3,2]
-  v += dpp_mov<0x4E>(v);   // quad_perm [2,3,0,1]
-  v += dpp_mov<0x141>(v);  // row_half_mirror
-  v += dpp_mov<0x140>(v);  // row_mirror: every lane of a 16-lane row holds the row's sum
-  return (lane_bcast(v, 0) + lane_bcast(v, 16)) + (lane_bcast(v, 32) + lane_bcast(v, 48));
-}
-
-// the sum over each 16-lane row of the wave, in every lane of that row
-template <class T> __device__ __forceinline__ T row_sum_dpp(T v) {
-  v += dpp_mov<0xB1>(v);
-  v += dpp_mov<0x4E>(v);
-  v += dpp_mov<0x141>(v);
-  v += dpp_mov<0x140>(v);
-  return v;
-}
-
-// sum over the block; every thread gets the result (two barriers)
-template <class T> __device__ T block_sum(T v, T* s_red) {
-  v = wave_sum(v);
-  __syncthreads();
-  if ((threadIdx.x & 63) == 0) s_red[threadIdx.x >> 6] = v;
-  __syncthreads();
-  T r = T(0);
-#pragma unroll
-  for (int w = 0; w < BLOCK / 64; w++) r += s_red[w];
-  return r;
-}
 
 // M[r0:m, c0:c1] -= tau * v (v^T M[r0:m, c0:c1]),  v = (1, V[r0+1, vc], ..., V[m-1, vc])
 // threads: 64 columns x 4 row slices per pass; s_v: VMAX, s_w: 4 x 64
@@ -134,7 +85,7 @@ __global__ __launch_bounds__(BLOCK) void geqrf_kernel(T* __restrict__ Aall, T* _
       const T x = A[(long long)i * n + k];
       part += x * x;
     }
-    const T xn2 = block_sum(part, s_red);
+    const T xn2 = wave::block_sum<BLOCK>(part, s_red);
     const T alpha = A[(long long)k * n + k];
     if (xn2 == T(0)) {  // dlarfg: H = I
       if (tid == 0) tau[k] = T(0);
@@ -157,32 +108,6 @@ __global__ __launch_bounds__(BLOCK) void geqrf_kernel(T* __restrict__ Aall, T* _
 }
 
 // ---- column-pivoted QR (dgeqp3 by its unblocked dlaqp2, every column) ---------------------------
-// (value, position) maximum: the larger value wins, the lower position among equal values; a total order, so
-// the result does not depend on the order in which pairs meet
-template <class T> __device__ __forceinline__ void argmax_take(T& v, int& p, T ov, int op) {
-  if (ov > v || (ov == v && op < p)) { v = ov; p = op; }
-}
-template <int CTRL, class T> __device__ __forceinline__ void argmax_dpp(T& v, int& p) {
-  const T ov = dpp_mov<CTRL>(v);
-  const int op = __builtin_amdgcn_update_dpp(0, p, CTRL, 0xf, 0xf, false);
-  argmax_take(v, p, ov, op);
-}
-// over the wave, in every lane: the DPP steps of wave_sum_dpp (the search sits on the critical path of every column)
-template <class T> __device__ __forceinline__ void wave_argmax(T& v, int& p) {
-  argmax_dpp<0xB1>(v, p);
-  argmax_dpp<0x4E>(v, p);
-  argmax_dpp<0x141>(v, p);
-  argmax_dpp<0x140>(v, p);  // every lane of a 16-lane row holds the row's pair
-  const T v0 = lane_bcast(v, 0);
-  const int p0 = __builtin_amdgcn_readlane(p, 0);
-  T bv = v0;
-  int bp = p0;
-  argmax_take(bv, bp, lane_bcast(v, 16), __builtin_amdgcn_readlane(p, 16));
-  argmax_take(bv, bp, lane_bcast(v, 32), __builtin_amdgcn_readlane(p, 32));
-  argmax_take(bv, bp, lane_bcast(v, 48), __builtin_amdgcn_readlane(p, 48));
-  v = bv; p = bp;
-}
-
 // vn1[c] = vn2[c] = ||M[r0:m, c]||_2 for the columns c0 <= c < c1 (all of them, or those whose vn2 holds the
 // marker -1): one row-contiguous pass, 64 columns x 4 row slices, the slices added in a fixed order.  s_w: 4 x 64
 template <class T>
@@ -249,17 +174,17 @@ __global__ __launch_bounds__(BLOCK) void geqp3_kernel(T* __restrict__ Aall, T* _
     for (int j = k + tid; j < n; j += BLOCK) {
       T v = vn1[j];
       if (k > 0 && v != T(0)) {
-        const T r = dabs(A[(long long)(k - 1) * n + j]) / v;
+        const T r = wave::dev_abs(A[(long long)(k - 1) * n + j]) / v;
         T t = T(1) - r * r;
         t = t > T(0) ? t : T(0);
         const T q = v / vn2[j];
         if (t * (q * q) <= tol3z) { vn2[j] = T(-1); recompute = 1; }
         else vn1[j] = v = v * sqrt(t);
       }
-      argmax_take(best, p, v == v ? v : T(-1), j);
+      wave::argmax_take(best, p, v == v ? v : T(-1), j);
     }
     for (int pass = 0; pass < 2; pass++) {
-      wave_argmax(best, p);
+      wave::wave_argmax_dpp(best, p);
       if ((tid & 63) == 0) { s_red[tid >> 6] = best; s_pos[tid >> 6] = p; }
       if (!__syncthreads_or(recompute)) break;  // (pass 1 arrives with recompute = 0)
       column_norms(A, n, k, m, k, n, true, vn1, vn2, s_w);
@@ -267,12 +192,12 @@ __global__ __launch_bounds__(BLOCK) void geqp3_kernel(T* __restrict__ Aall, T* _
       best = T(-2); p = n;
       for (int j = k + tid; j < n; j += BLOCK) {
         const T v = vn1[j];
-        argmax_take(best, p, v == v ? v : T(-1), j);
+        wave::argmax_take(best, p, v == v ? v : T(-1), j);
       }
     }
     best = s_red[0]; p = s_pos[0];
 #pragma unroll
-    for (int w = 1; w < BLOCK / 64; w++) argmax_take(best, p, s_red[w], s_pos[w]);
+    for (int w = 1; w < BLOCK / 64; w++) wave::argmax_take(best, p, s_red[w], s_pos[w]);
     // (thread 0 scanned position k itself, so k <= p < n whatever the norms hold)
     // the swap and the squared norm of the new column k below the diagonal, in one pass over the rows
     T part = T(0);
@@ -288,7 +213,7 @@ __global__ __launch_bounds__(BLOCK) void geqp3_kernel(T* __restrict__ Aall, T* _
       const int jt = jp[p]; jp[p] = jp[k]; jp[k] = jt;
       vn1[p] = vn1[k]; vn2[p] = vn2[k];
     }
-    const T xn2 = block_sum(part, s_red);
+    const T xn2 = wave::block_sum<BLOCK>(part, s_red);
     const T alpha = A[(long long)k * n + k];
     if (xn2 == T(0)) {  // dlarfg: H = I
       if (tid == 0) tau[k] = T(0);
@@ -367,7 +292,7 @@ __global__ __launch_bounds__(SVD_BLOCK) void svd_rows_kernel(T* __restrict__ Xal
       for (int i = wid; i < r; i += SVD_BLOCK / 64) {
         T a = T(0);
         for (int j = lane; j < c; j += 64) { const T u = X[(long long)i * c + j]; a += u * u; }
-        a = wave_sum_dpp(a);
+        a = wave::wave_sum_dpp_pairwise(a);
         if (lane == 0) s_n2[i] = a;
       }
     }
@@ -404,7 +329,7 @@ __global__ __launch_bounds__(SVD_BLOCK) void svd_rows_kernel(T* __restrict__ Xal
             g += xu[t] * xv[t];
           }
           const T a = s_n2[p], b = s_n2[q];
-          g = row_sum_dpp(g);
+          g = wave::row_sum_dpp(g);
           const bool rotate = real && g != T(0) && g * g > eps * eps * a * b;
           const float gf = rotate ? (float)g : 1.f;
           const float zf = (float)(b - a) / (2.f * gf);
@@ -412,7 +337,7 @@ __global__ __launch_bounds__(SVD_BLOCK) void svd_rows_kernel(T* __restrict__ Xal
           T tt = (T)tf;
           if (rotate && !(tf != 0.f && tf == tf)) {
             const T zeta = (b - a) / (T(2) * g);
-            tt = (zeta >= T(0) ? T(1) : T(-1)) / (dabs(zeta) + sqrt(T(1) + zeta * zeta));
+            tt = (zeta >= T(0) ? T(1) : T(-1)) / (wave::dev_abs(zeta) + sqrt(T(1) + zeta * zeta));
           }
           if (!rotate) tt = T(0);
           T cs;
@@ -438,8 +363,8 @@ __global__ __launch_bounds__(SVD_BLOCK) void svd_rows_kernel(T* __restrict__ Xal
               if (want_vectors && j < r) { pp[j] = cs * pu[t] - sn * pv[t]; pq[j] = sn * pu[t] + cs * pv[t]; }
             }
             T na = a - tt * g, nb = b + tt * g;
-            if (!(na > T(0.01) * a)) na = row_sum_dpp(za);  // (cancellation: summed again from the rotated row)
-            if (!(nb > T(0.01) * b)) nb = row_sum_dpp(zb);
+            if (!(na > T(0.01) * a)) na = wave::row_sum_dpp(za);  // (cancellation: summed again from the rotated row)
+            if (!(nb > T(0.01) * b)) nb = wave::row_sum_dpp(zb);
             if (l16 == 0) { s_n2[p] = na; s_n2[q] = nb; s_rot = 1; }
           }
         }
@@ -472,7 +397,7 @@ __global__ __launch_bounds__(SVD_BLOCK) void svd_rows_kernel(T* __restrict__ Xal
 #pragma unroll
           for (int t = 0; t < SVD_CACHE; t++) g += xu[t] * xv[t];
           const T a = s_n2[p], b = s_n2[q];
-          g = wave_sum_dpp(g);
+          g = wave::wave_sum_dpp_pairwise(g);
           if (g == T(0) || g * g <= eps * eps * a * b) continue;
           // the angle in single precision (it steers convergence only), the rotation in working precision
           const float zf = (float)(b - a) / (2.f * (float)g);
@@ -481,7 +406,7 @@ __global__ __launch_bounds__(SVD_BLOCK) void svd_rows_kernel(T* __restrict__ Xal
           if (!(tf != 0.f && tf == tf)) {
             // out of single precision's range (a graded matrix: |g| or the ratio under / overflows): the same formula in T
             const T zeta = (b - a) / (T(2) * g);
-            tt = (zeta >= T(0) ? T(1) : T(-1)) / (dabs(zeta) + sqrt(T(1) + zeta * zeta));
+            tt = (zeta >= T(0) ? T(1) : T(-1)) / (wave::dev_abs(zeta) + sqrt(T(1) + zeta * zeta));
           }
           T cs;
           if constexpr (sizeof(T) == 8) {
@@ -510,13 +435,13 @@ __global__ __launch_bounds__(SVD_BLOCK) void svd_rows_kernel(T* __restrict__ Xal
             T z = T(0);
 #pragma unroll
             for (int t = 0; t < SVD_CACHE; t++) z += xu[t] * xu[t];
-            na = wave_sum_dpp(z);
+            na = wave::wave_sum_dpp_pairwise(z);
           }
           if (!(nb > T(0.01) * b)) {
             T z = T(0);
 #pragma unroll
             for (int t = 0; t < SVD_CACHE; t++) z += xv[t] * xv[t];
-            nb = wave_sum_dpp(z);
+            nb = wave::wave_sum_dpp_pairwise(z);
           }
           if (lane == 0) { s_n2[p] = na; s_n2[q] = nb; s_rot = 1; }
           continue;
@@ -526,10 +451,10 @@ __global__ __launch_bounds__(SVD_BLOCK) void svd_rows_kernel(T* __restrict__ Xal
           const T u = xp[j], v = xq[j];
           a += u * u; b += v * v; g += u * v;
         }
-        a = wave_sum(a); b = wave_sum(b); g = wave_sum(g);
-        if (g == T(0) || dabs(g) <= eps * sqrt(a) * sqrt(b)) continue;
+        a = wave::wave_sum(a); b = wave::wave_sum(b); g = wave::wave_sum(g);
+        if (g == T(0) || wave::dev_abs(g) <= eps * sqrt(a) * sqrt(b)) continue;
         const T zeta = (b - a) / (T(2) * g);
-        const T t = (zeta >= T(0) ? T(1) : T(-1)) / (dabs(zeta) + sqrt(T(1) + zeta * zeta));
+        const T t = (zeta >= T(0) ? T(1) : T(-1)) / (wave::dev_abs(zeta) + sqrt(T(1) + zeta * zeta));
         const T cs = T(1) / sqrt(T(1) + t * t), sn = cs * t;
         for (int j = lane; j < c; j += 64) {
           const T u = xp[j], v = xq[j];
@@ -555,7 +480,7 @@ __global__ __launch_bounds__(SVD_BLOCK) void svd_rows_kernel(T* __restrict__ Xal
   for (int i = wid; i < r; i += SVD_BLOCK / 64) {
     T a = T(0);
     for (int j = lane; j < c; j += 64) { const T u = X[(long long)i * c + j]; a += u * u; }
-    a = wave_sum(a);
+    a = wave::wave_sum(a);
     if (lane == 0) s_norm[i] = sqrt(a);
   }
   __syncthreads();
@@ -566,7 +491,7 @@ __global__ __launch_bounds__(SVD_BLOCK) void svd_rows_kernel(T* __restrict__ Xal
     const T si = s_norm[i];
     int rank = 0;
     for (int j = lane; j < r; j += 64) rank += (s_norm[j] > si || (s_norm[j] == si && j < i)) ? 1 : 0;
-    rank = (int)wave_sum((T)rank);
+    rank = (int)wave::wave_sum((T)rank);
     if (lane == 0) S[rank] = si;
     if (want_vectors) {
       const T inv = si > T(0) ? T(1) / si : T(0);
@@ -618,7 +543,7 @@ __global__ void gttrf_kernel(long long batch, int n, T* __restrict__ dl, T* __re
   for (int i = 0; i < n - 2; i++) du2[i] = T(0);
   for (int i = 0; i < n - 1; i++) {
     const bool last = i == n - 2;
-    if (dabs(d[i]) >= dabs(dl[i])) {
+    if (wave::dev_abs(d[i]) >= wave::dev_abs(dl[i])) {
       if (d[i] != T(0)) {
         const T fact = dl[i] / d[i];
         dl[i] = fact;

@@ -17,6 +17,7 @@
 // a rotation; no convergence within MAX_SWEEPS raises bit 1 of the device error word
 // (scipy raises LinAlgError when LAPACK reports non-convergence).
 #include "common.h"
+#include "wave_device.h"
 
 #include <cstring>
 #include <utility>
@@ -70,8 +71,7 @@ __global__ __launch_bounds__(BLOCK) void eigh_jacobi_kernel(const T* __restrict_
       V[i * ld + j] = i == j ? T(1) : T(0);
       fro += a * a;
     }
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) fro += __shfl_xor(fro, o);
+  fro = wave::wave_sum(fro);
   if (lane == 0) s_red[wid] = fro;
   if (tid == 0) s_rot = 0;
   __syncthreads();
@@ -216,79 +216,6 @@ __device__ __forceinline__ T eigh_sym_at(const T* A, long long n, int lower, lon
   return A[r * n + c];
 }
 
-template <int CTRL>
-__device__ __forceinline__ double eigh_dpp_f64(double v) {
-  const int lo = __builtin_amdgcn_update_dpp(0, __double2loint(v), CTRL, 0xf, 0xf, false);
-  const int hi = __builtin_amdgcn_update_dpp(0, __double2hiint(v), CTRL, 0xf, 0xf, false);
-  return __hiloint2double(hi, lo);
-}
-template <int CTRL>
-__device__ __forceinline__ float eigh_dpp_f32(float v) {
-  return __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), CTRL, 0xf, 0xf, false));
-}
-// the sum over the 64 lanes, in every lane (the same value, bit for bit: fixed tree)
-__device__ __forceinline__ double eigh_wave_sum(double v) {
-  v += eigh_dpp_f64<0xB1>(v);   // quad_perm [1,0,3,2]
-  v += eigh_dpp_f64<0x4E>(v);   // quad_perm [2,3,0,1]
-  v += eigh_dpp_f64<0x141>(v);  // row_half_mirror
-  v += eigh_dpp_f64<0x140>(v);  // row_mirror: every lane of a 16-lane row holds the row's sum
-  const int lo = __double2loint(v), hi = __double2hiint(v);
-  double t = 0.0;
-#pragma unroll
-  for (int r = 0; r < 4; r++) t += __hiloint2double(__builtin_amdgcn_readlane(hi, 16 * r), __builtin_amdgcn_readlane(lo, 16 * r));
-  return t;
-}
-__device__ __forceinline__ float eigh_wave_sum(float v) {
-  v += eigh_dpp_f32<0xB1>(v);
-  v += eigh_dpp_f32<0x4E>(v);
-  v += eigh_dpp_f32<0x141>(v);
-  v += eigh_dpp_f32<0x140>(v);
-  const int b = __float_as_int(v);
-  float t = 0.f;
-#pragma unroll
-  for (int r = 0; r < 4; r++) t += __int_as_float(__builtin_amdgcn_readlane(b, 16 * r));
-  return t;
-}
-
-// the sum over each 16-lane row of the wave, in every lane of that row: four DPP steps, nothing else
-__device__ __forceinline__ double eigh_row_sum(double v) {
-  v += eigh_dpp_f64<0xB1>(v);
-  v += eigh_dpp_f64<0x4E>(v);
-  v += eigh_dpp_f64<0x141>(v);
-  v += eigh_dpp_f64<0x140>(v);
-  return v;
-}
-__device__ __forceinline__ float eigh_row_sum(float v) {
-  v += eigh_dpp_f32<0xB1>(v);
-  v += eigh_dpp_f32<0x4E>(v);
-  v += eigh_dpp_f32<0x141>(v);
-  v += eigh_dpp_f32<0x140>(v);
-  return v;
-}
-// the sum over each 32-lane half of the wave, in every lane of that half
-__device__ __forceinline__ double eigh_half_sum(double v) {
-  v += eigh_dpp_f64<0xB1>(v);
-  v += eigh_dpp_f64<0x4E>(v);
-  v += eigh_dpp_f64<0x141>(v);
-  v += eigh_dpp_f64<0x140>(v);
-  const int lo = __double2loint(v), hi = __double2hiint(v);
-  const double h0 = __hiloint2double(__builtin_amdgcn_readlane(hi, 0), __builtin_amdgcn_readlane(lo, 0)) +
-                    __hiloint2double(__builtin_amdgcn_readlane(hi, 16), __builtin_amdgcn_readlane(lo, 16));
-  const double h1 = __hiloint2double(__builtin_amdgcn_readlane(hi, 32), __builtin_amdgcn_readlane(lo, 32)) +
-                    __hiloint2double(__builtin_amdgcn_readlane(hi, 48), __builtin_amdgcn_readlane(lo, 48));
-  return (threadIdx.x & 32) ? h1 : h0;
-}
-__device__ __forceinline__ float eigh_half_sum(float v) {
-  v += eigh_dpp_f32<0xB1>(v);
-  v += eigh_dpp_f32<0x4E>(v);
-  v += eigh_dpp_f32<0x141>(v);
-  v += eigh_dpp_f32<0x140>(v);
-  const int b = __float_as_int(v);
-  const float h0 = __int_as_float(__builtin_amdgcn_readlane(b, 0)) + __int_as_float(__builtin_amdgcn_readlane(b, 16));
-  const float h1 = __int_as_float(__builtin_amdgcn_readlane(b, 32)) + __int_as_float(__builtin_amdgcn_readlane(b, 48));
-  return (threadIdx.x & 32) ? h1 : h0;
-}
-
 constexpr int EIGH1_BLOCK = 1024;
 constexpr int EIGH1_MAXN = 192;  // the kernel's per-row LDS arrays
 constexpr int EIGH1_UP = 9;      // row values per lane of a 16-lane row: n <= 144 (fp64 fits the LDS up to n = 138)
@@ -318,10 +245,10 @@ __global__ __launch_bounds__(EIGH1_BLOCK) void eigh_onesided_kernel(const T* __r
       fro += a * a;
       rs += a < 0.0 ? -a : a;
     }
-    rs = eigh_wave_sum(rs);
+    rs = wave::wave_sum_dpp_sequential(rs);
     rmax = rs > rmax ? rs : rmax;
   }
-  fro = eigh_wave_sum(fro);
+  fro = wave::wave_sum_dpp_sequential(fro);
   if (lane == 0) { s_red[0][wid] = fro; s_red[1][wid] = rmax; }
   if (tid == 0) s_rot = 0;
   __syncthreads();
@@ -346,7 +273,7 @@ __global__ __launch_bounds__(EIGH1_BLOCK) void eigh_onesided_kernel(const T* __r
     for (int j = wid; j < n; j += NW) {
       T a = T(0);
       for (int k = lane; k < n; k += 64) { const T g = G[j * ld + k]; a += g * g; }
-      a = eigh_wave_sum(a);
+      a = wave::wave_sum_dpp_sequential(a);
       if (lane == 0) s_n2[j] = a;
     }
     __syncthreads();
@@ -374,7 +301,7 @@ __global__ __launch_bounds__(EIGH1_BLOCK) void eigh_onesided_kernel(const T* __r
           c += x[u] * y[u];
         }
         const T a = s_n2[p], b = s_n2[q];
-        c = eigh_row_sum(c);  // the sum over this lane's 16-lane row
+        c = wave::row_sum_dpp(c);  // the sum over this lane's 16-lane row
         const bool rotate = real && (c * c > tol * tol * a * b);
         // the rotation ANGLE in single precision (it only steers convergence: v_rcp_f32 / v_sqrt_f32 instead of three
         // fp64 divisions and a square root), the rotation itself — cs = (1 + t^2)^-1/2, sn = t cs — in working
@@ -426,7 +353,7 @@ __global__ __launch_bounds__(EIGH1_BLOCK) void eigh_onesided_kernel(const T* __r
   for (int j = wid; j < n; j += NW) {
     T a = T(0);
     for (int k = lane; k < n; k += 64) { const T g = G[j * ld + k]; a += g * g; }
-    a = eigh_wave_sum(a);
+    a = wave::wave_sum_dpp_sequential(a);
     if (lane == 0) { const T nr = sqrt(a); s_nrm[j] = nr; s_lam[j] = nr - sigma; }
   }
   __syncthreads();
@@ -486,8 +413,7 @@ __global__ __launch_bounds__(256) void eigh_rowsum_kernel(const T* __restrict__ 
     const double a = (double)eigh_sym_at(A, n, lower, i, j);
     s += a < 0.0 ? -a : a;
   }
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) s += __shfl_xor(s, o);
+  s = wave::wave_sum(s);
   if (lane == 0 && s == s) atomicMax(maxbits, (unsigned long long)__double_as_longlong(s));
 }
 
@@ -502,8 +428,7 @@ __global__ __launch_bounds__(256) void eigh_absrow_kernel(const T* __restrict__ 
     const double a = (double)Cm[i * N + j];
     s += a < 0.0 ? -a : a;
   }
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) s += __shfl_xor(s, o);
+  s = wave::wave_sum(s);
   if (lane == 0 && s == s) atomicMax(maxbits, (unsigned long long)__double_as_longlong(s));
 }
 
@@ -563,8 +488,7 @@ __global__ __launch_bounds__(256) void eigh_offdiag_kernel(const T* __restrict__
       best = 1.f;
     }
   }
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) { const float ov = __shfl_xor(best, o); best = ov > best ? ov : best; }
+  best = wave::wave_max(best);
   if ((threadIdx.x & 63) == 0 && best > 0.f) atomicMax(maxbits, __float_as_uint(best));
 }
 
@@ -577,8 +501,7 @@ __global__ __launch_bounds__(256) void eigh_lambda_kernel(const T* __restrict__ 
   if (j >= N) return;
   T s = T(0);
   for (long long i = lane; i < N; i += 64) s += Vt[j * N + i] * Gt[j * N + i];
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) s += __shfl_xor(s, o);
+  s = wave::wave_sum(s);
   if (lane == 0) lam[j] = s - sigma[0];
 }
 
@@ -905,8 +828,7 @@ __global__ __launch_bounds__(256) void svdb_absmax_kernel(const T* __restrict__ 
     if (!(a <= 1.7976931348623157e308)) nf = 1;
     else best = a > best ? a : best;
   }
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) { const double ov = __shfl_xor(best, o); best = ov > best ? ov : best; }
+  best = wave::wave_max(best);
   if ((threadIdx.x & 63) == 0 && best > 0.0) atomicMax(maxbits, (unsigned long long)__double_as_longlong(best));
   if (nf) atomicOr(bad, 1);
 }

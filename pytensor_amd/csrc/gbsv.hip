@@ -19,11 +19,12 @@
 //     kernel, from (kl, ku).  While (kl + 1) * nrhs <= 64 the wave also keeps the kl + 1 rows of X a step touches in
 //     registers, a lane per element (kl + ku + 1 rows on the way back): a finished row is stored, the next one comes
 //     from blocks fetched ahead (RowFeed), so a step waits for LDS only, never for memory.
-//   * pivot = the first maximum of pivot_abs (a NaN ranks as +inf, as in lu_batched.hip) among rows k .. k+kl of
+//   * pivot = the first maximum of pivot_abs (a NaN ranks as +inf, wave_device.h) among rows k .. k+kl of
 //     column k, LAPACK's idamax order; multipliers scaled by the reciprocal pivot like dgbtf2.  An exactly zero or
 //     NaN pivot NaN-fills the item's solution.  Workgroups never wait for each other: no flags, no spin loops; the
 //     only atomics are the scan's atomicMax.
 #include "common.h"
+#include "wave_device.h"
 
 namespace {
 
@@ -31,15 +32,6 @@ constexpr int WG = 256;
 // dynamic LDS of the band layout: what decomp.hip leaves its QR panels beside the static arrays
 constexpr size_t GB_LDS_MAX = 160 * 1024 - 12 * 1024;
 constexpr int NARROW_KL = 16, NARROW_KV = 32;  // kl + 1 <= 16 rows and kl + ku + 1 <= 32 columns per step: one wave
-
-template <class T> __device__ __forceinline__ T dev_abs(T x) { return x < T(0) ? -x : x; }
-template <class T> __device__ __forceinline__ T pivot_abs(T x) { return x != x ? T(INFINITY) : dev_abs(x); }
-
-__device__ __forceinline__ int wave_max(int v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v = max(v, __shfl_xor(v, o, 64));
-  return v;
-}
 
 // ---- band scan ------------------------------------------------------------------------------------------------
 // element (s, f) of item m at A + m*sAb + s*sS + f*sF (f: the axis across the lanes).  lo = max(s - f), hi = max(f - s)
@@ -74,8 +66,8 @@ __global__ __launch_bounds__(WG) void band_scan_kernel(const T* __restrict__ A, 
           if (!(p[(long long)f * sF] == T(0))) { lo = max(lo, s - f); hi = max(hi, f - s); }
       }
     }
-    lo = wave_max(lo);
-    hi = wave_max(hi);
+    lo = wave::wave_max(lo);
+    hi = wave::wave_max(hi);
     if ((threadIdx.x & 63) == 0) {
       const int kl = col_fast ? lo : hi, ku = col_fast ? hi : lo;
       if (kl > 0) atomicMax(out + 2 * m, kl);
@@ -184,7 +176,7 @@ __device__ bool gb_eliminate(const Acc M, const int n, const int kl, const int k
     int bi = 0x7fffffff;
     if constexpr (NARROW) {
       // at most 16 candidates, one per lane: a butterfly over just the lanes that hold one, lane 0 tells the rest
-      if (tid <= km) { best = pivot_abs(M.at(k + tid, k)); bi = tid; }
+      if (tid <= km) { best = wave::pivot_abs(M.at(k + tid, k)); bi = tid; }
       for (int o = 1; o <= km; o <<= 1) {
         const T ov = __shfl_xor(best, o, 64);
         const int oi = __shfl_xor(bi, o, 64);
@@ -193,7 +185,7 @@ __device__ bool gb_eliminate(const Acc M, const int n, const int kl, const int k
       bi = __builtin_amdgcn_readfirstlane(bi);
     } else {
       for (int r = tid; r <= km; r += NT) {
-        const T v = pivot_abs(M.at(k + r, k));
+        const T v = wave::pivot_abs(M.at(k + r, k));
         if (v > best) { best = v; bi = r; }
       }
 #pragma unroll

@@ -16,6 +16,7 @@
 // Outputs: the packed factors, the row permutation as a gather vector (row i of P*A is row
 // perm[i] of A), its sign (0 when singular) and log|det|.
 #include "common.h"
+#include "wave_device.h"
 
 #include <cstring>
 #include <type_traits>
@@ -24,12 +25,6 @@
 namespace {
 
 constexpr int BLOCK = 256;
-
-template <class T> __device__ __forceinline__ T dev_abs(T x) { return x < T(0) ? -x : x; }
-// |x| for the pivot searches, with NaN ranked as +inf: every row still in the search is a candidate (a column of NaN
-// would otherwise leave none, and the "no candidate" key would index past the matrix), and a NaN pivot carries the
-// NaN into the factors as LAPACK's idamax-based getrf does
-template <class T> __device__ __forceinline__ T pivot_abs(T x) { return x != x ? T(INFINITY) : dev_abs(x); }
 
 template <class T>
 __global__ __launch_bounds__(BLOCK) void getrf_kernel(T* __restrict__ LUout,
@@ -61,7 +56,7 @@ __global__ __launch_bounds__(BLOCK) void getrf_kernel(T* __restrict__ LUout,
     T best = T(-1);
     int bi = k;
     for (int i = k + tid; i < n; i += BLOCK) {
-      const T v = pivot_abs(W[i * ld + k]);
+      const T v = wave::pivot_abs(W[i * ld + k]);
       if (v > best) { best = v; bi = i; }
     }
 #pragma unroll
@@ -115,7 +110,7 @@ __global__ __launch_bounds__(BLOCK) void getrf_kernel(T* __restrict__ LUout,
     for (int i = 0; i < n; i++) {
       const T d = W[i * ld + i];
       if (d < T(0)) sg = -sg;
-      la += log(dev_abs(d));
+      la += log(wave::dev_abs(d));
     }
     if (singular) { sg = T(0); la = -__builtin_huge_val(); }
     sign_out[mat] = sg;
@@ -135,26 +130,6 @@ __global__ __launch_bounds__(BLOCK) void getrf_kernel(T* __restrict__ LUout,
 // multipliers go to a staging matrix in global memory, so the update needs no per-element
 // tests), the owners of the next column publish that, one barrier.  Two barriers and ~3 LDS
 // reads per thread-row and column instead of a read-modify-write sweep of the trailing block.
-template <int CTRL, int ROW_MASK>
-__device__ __forceinline__ int dpp_or_own(int own) {
-  return __builtin_amdgcn_update_dpp(own, own, CTRL, ROW_MASK, 0xf, false);
-}
-
-// wave-wide arg-max of (v, key): larger v wins, ties go to the smaller key; result in lane 63
-template <class T, int CTRL, int ROW_MASK>
-__device__ __forceinline__ void argmax_step(T& v, int& key) {
-  T ov;
-  if constexpr (sizeof(T) == 8) {
-    const int lo = dpp_or_own<CTRL, ROW_MASK>(__double2loint(v));
-    const int hi = dpp_or_own<CTRL, ROW_MASK>(__double2hiint(v));
-    ov = __hiloint2double(hi, lo);
-  } else {
-    ov = __int_as_float(dpp_or_own<CTRL, ROW_MASK>(__float_as_int(v)));
-  }
-  const int ok = dpp_or_own<CTRL, ROW_MASK>(key);
-  if (ov > v || (ov == v && ok < key)) { v = ov; key = ok; }
-}
-
 template <class T, int NB>
 __global__ __launch_bounds__(BLOCK) void getrf_reg_kernel(T* __restrict__ LUout, const T* __restrict__ Ain,
                                                          long long* __restrict__ perm_out,
@@ -199,18 +174,18 @@ __global__ __launch_bounds__(BLOCK) void getrf_reg_kernel(T* __restrict__ LUout,
       if (rho < n) {
         const int p = s_pos[rho];
         if (p >= k) {
-          const T x = pivot_abs(col[rho]);
+          const T x = wave::pivot_abs(col[rho]);
           const int ky = p * 256 + rho;
           if (x > v || (x == v && ky < key)) { v = x; key = ky; }
         }
       }
     }
-    argmax_step<T, 0x111, 0xf>(v, key);  // row_shr:1
-    argmax_step<T, 0x112, 0xf>(v, key);  // row_shr:2
-    argmax_step<T, 0x114, 0xf>(v, key);  // row_shr:4
-    argmax_step<T, 0x118, 0xf>(v, key);  // row_shr:8
-    argmax_step<T, 0x142, 0xa>(v, key);  // row_bcast:15 into rows 1, 3
-    argmax_step<T, 0x143, 0xc>(v, key);  // row_bcast:31 into rows 2, 3
+    wave::argmax_dpp_or_own_step<0x111, 0xf>(v, key);  // row_shr:1
+    wave::argmax_dpp_or_own_step<0x112, 0xf>(v, key);  // row_shr:2
+    wave::argmax_dpp_or_own_step<0x114, 0xf>(v, key);  // row_shr:4
+    wave::argmax_dpp_or_own_step<0x118, 0xf>(v, key);  // row_shr:8
+    wave::argmax_dpp_or_own_step<0x142, 0xa>(v, key);  // row_bcast:15 into rows 1, 3
+    wave::argmax_dpp_or_own_step<0x143, 0xc>(v, key);  // row_bcast:31 into rows 2, 3
     key = __builtin_amdgcn_readlane(key, 63);
     const int rho = key & 255, q = key >> 8;
     const T piv = col[rho];
@@ -289,7 +264,7 @@ __global__ __launch_bounds__(BLOCK) void getrf_reg_kernel(T* __restrict__ LUout,
   for (int i = tid; i < n; i += BLOCK) {
     const T d = s_piv[i];
     neg += d < T(0);
-    la += log(dev_abs(d));
+    la += log(wave::dev_abs(d));
   }
 #pragma unroll
   for (int o = 32; o > 0; o >>= 1) { la += __shfl_xor(la, o); neg += __shfl_xor(neg, o); }
@@ -359,16 +334,6 @@ __device__ __forceinline__ bool lu_poll(const unsigned long long* slot, unsigned
   return (bits ^ b) == LU_MAGIC;
 }
 
-template <class T>
-__device__ __forceinline__ void wave_argmax(T& v, int& key) {  // result valid in lane 63
-  argmax_step<T, 0x111, 0xf>(v, key);
-  argmax_step<T, 0x112, 0xf>(v, key);
-  argmax_step<T, 0x114, 0xf>(v, key);
-  argmax_step<T, 0x118, 0xf>(v, key);
-  argmax_step<T, 0x142, 0xa>(v, key);
-  argmax_step<T, 0x143, 0xc>(v, key);
-}
-
 template <class F, int... Js>
 __device__ __forceinline__ bool lu_for_each_column(F&& f, std::integer_sequence<int, Js...>) {
   return (f(std::integral_constant<int, Js>{}) && ...);
@@ -398,9 +363,9 @@ __global__ __launch_bounds__(BLOCK) void lu_panel_kernel(T* __restrict__ W, long
     if (j < pw) {  // (uniform: the last panel may be narrower)
     const int k = k0 + j;
     // ---- this workgroup's candidate: largest |a_ik| among its rows i >= k, first such row
-    T v = (have && grow >= k) ? pivot_abs(a[j]) : T(-1);
+    T v = (have && grow >= k) ? wave::pivot_abs(a[j]) : T(-1);
     int key = (have && grow >= k) ? (int)grow : 0x7fffffff;
-    wave_argmax<T>(v, key);
+    wave::wave_argmax_dpp_lane63(v, key);
     if (lane == 63) { s_val[wid] = v; s_row[wid] = key; }
     __syncthreads();
     T bv = s_val[0];
@@ -444,7 +409,7 @@ __global__ __launch_bounds__(BLOCK) void lu_panel_kernel(T* __restrict__ W, long
             if (x > cv || (x == cv && r < cr)) { cv = x; cr = r; }
           }
         }
-        wave_argmax<T>(cv, cr);
+        wave::wave_argmax_dpp_lane63(cv, cr);
         const int p = __builtin_amdgcn_readlane(cr, 63);
         const int wstar = ok ? (p - k0) / BLOCK : 0;
         if (ok && lane < LB) {
@@ -578,7 +543,7 @@ __global__ __launch_bounds__(BLOCK) void lu_finish_kernel(const T* __restrict__ 
   for (int i = tid; i < n; i += BLOCK) {
     const T d = W[(long long)i * ld + i];
     neg += d < T(0);
-    la += log(dev_abs(d));
+    la += log(wave::dev_abs(d));
     neg += ipiv[i] != i;
   }
 #pragma unroll
@@ -754,9 +719,9 @@ __global__ __launch_bounds__(TB) void lu_panel2_kernel(T* __restrict__ W, long l
       const unsigned long long tag = LU_MAGIC ^ ((unsigned long long)(k + 1) * LU_EPOCH_MUL) ^ nonce;
       // ---- A: this workgroup's candidate: largest |a_ik| among its rows not yet pivoted, first in the current order
       const bool act = have && !done;
-      T v = act ? pivot_abs(a[0]) : T(-1);
+      T v = act ? wave::pivot_abs(a[0]) : T(-1);
       int key = act ? cur : 0x7fffffff;
-      wave_argmax<T>(v, key);
+      wave::wave_argmax_dpp_lane63(v, key);
       const int wkey = __builtin_amdgcn_readlane(key, 63);
       if (act && cur == wkey) {
 #pragma unroll
@@ -823,7 +788,7 @@ __global__ __launch_bounds__(TB) void lu_panel2_kernel(T* __restrict__ W, long l
               if (base + g * NPOLL < nW) {  // (uniform)
                 T x;
                 lu_from_bits(lane_bcast_u64<2>(b0[g]), x);  // entry 0 of the candidate row: its column-k value
-                x = pivot_abs(x);
+                x = wave::pivot_abs(x);
                 const int r = (int)lane_bcast_u64<0>(b0[g]);
                 if (r != 0x7fffffff && (x > cv || (x == cv && r < cr))) { cv = x; cr = r; best0 = b0[g]; best1 = b1[g]; }
               }

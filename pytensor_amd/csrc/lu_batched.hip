@@ -25,6 +25,7 @@
 // The composed tier above n = 64 (getrf, this file's batched row gather, two trsm) needs P*B — or P*I — for a whole
 // batch in one launch: laswp_batched_kernel.
 #include "common.h"
+#include "wave_device.h"
 
 #include <type_traits>
 
@@ -32,10 +33,6 @@ namespace {
 
 constexpr int WG = 256;  // 4 independent waves
 constexpr int CH = 8;    // right-hand-side columns per pass through the factors
-
-template <class T> __device__ __forceinline__ T dev_abs(T x) { return x < T(0) ? -x : x; }
-// NaN ranked as +inf, as in lu.hip: a NaN becomes the pivot and spreads, as LAPACK's idamax-based getrf has it
-template <class T> __device__ __forceinline__ T pivot_abs(T x) { return x != x ? T(INFINITY) : dev_abs(x); }
 
 // f(integral_constant<int, I>) for I = I0 .. N-1: the column index of every step is a compile-time constant, so
 // the row array is only ever indexed by constants (a loop the optimiser leaves rolled would send it to scratch)
@@ -50,18 +47,8 @@ __device__ __forceinline__ void static_for(F&& f) {
 // value of lane `src` of this lane's group.  A 64-lane group's source is wave-uniform: v_readlane, no LDS crossbar.
 template <int G, class T>
 __device__ __forceinline__ T group_bcast(T x, int src, int gbase) {
-  if constexpr (G == 64) {
-    const int s = __builtin_amdgcn_readfirstlane(src);
-    if constexpr (sizeof(T) == 8) {
-      const int lo = __builtin_amdgcn_readlane(__double2loint(x), s);
-      const int hi = __builtin_amdgcn_readlane(__double2hiint(x), s);
-      return __hiloint2double(hi, lo);
-    } else {
-      return __int_as_float(__builtin_amdgcn_readlane(__float_as_int(x), s));
-    }
-  } else {
-    return __shfl(x, gbase + src, 64);
-  }
+  if constexpr (G == 64) return wave::lane_bcast(x, __builtin_amdgcn_readfirstlane(src));
+  else return __shfl(x, gbase + src, 64);
 }
 
 template <class T, int G, int NR>
@@ -101,7 +88,7 @@ __global__ __launch_bounds__(WG) void gesv_wave_kernel(long long batch, int n, l
       static_for<0, NR>([&](auto kc) {
         constexpr int k = decltype(kc)::value;
         if (k >= n) return;
-        T v = (row && pos >= k) ? pivot_abs(a[k]) : T(-1);
+        T v = (row && pos >= k) ? wave::pivot_abs(a[k]) : T(-1);
         int key = (pos << 6) | lig;
 #pragma unroll
         for (int ob = 0; (1 << ob) < G; ob++) {

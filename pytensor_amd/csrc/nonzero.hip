@@ -7,34 +7,13 @@
 // total), ordered write.  The output length is data dependent: the total is left in device
 // memory and read back by the caller (such graphs are not captured into hipGraphs).
 #include "common.h"
+#include "wave_device.h"
 
 namespace {
 
 constexpr int BLOCK = 256;
 constexpr int ITEMS = 16;  // consecutive elements per thread
 constexpr int TILE = BLOCK * ITEMS;
-
-__device__ __forceinline__ long long block_exclusive_scan(long long v, long long* total) {
-  __shared__ long long s_wave[BLOCK / 64];
-  const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
-  long long incl = v;
-#pragma unroll
-  for (int o = 1; o < 64; o <<= 1) {
-    const long long t = __shfl_up(incl, o);
-    if (lane >= o) incl += t;
-  }
-  if (lane == 63) s_wave[wid] = incl;
-  __syncthreads();
-  long long base = 0, all = 0;
-#pragma unroll
-  for (int w = 0; w < BLOCK / 64; w++) {
-    if (w < wid) base += s_wave[w];
-    all += s_wave[w];
-  }
-  __syncthreads();
-  *total = all;
-  return base + incl - v;
-}
 
 __global__ __launch_bounds__(BLOCK) void nz_count_kernel(const unsigned char* __restrict__ m, long long n,
                                                         long long* __restrict__ counts) {
@@ -44,7 +23,7 @@ __global__ __launch_bounds__(BLOCK) void nz_count_kernel(const unsigned char* __
   for (int j = 0; j < ITEMS; j++)
     if (start + j < n) c += m[start + j] != 0;
   long long total;
-  block_exclusive_scan(c, &total);
+  wave::block_exclusive_scan<BLOCK>(c, &total);
   if (threadIdx.x == 0) counts[blockIdx.x] = total;
 }
 
@@ -55,7 +34,7 @@ __global__ __launch_bounds__(BLOCK) void nz_scan_kernel(long long* __restrict__ 
     const long long i = base + threadIdx.x;
     const long long v = i < nb ? counts[i] : 0;
     long long chunk;
-    const long long ex = block_exclusive_scan(v, &chunk);
+    const long long ex = wave::block_exclusive_scan<BLOCK>(v, &chunk);
     if (i < nb) counts[i] = carry + ex;
     carry += chunk;
   }
@@ -71,7 +50,7 @@ __global__ __launch_bounds__(BLOCK) void nz_write_kernel(const unsigned char* __
   for (int j = 0; j < ITEMS; j++)
     if (start + j < n && m[start + j] != 0) bits |= 1u << j;
   long long total;
-  long long pos = offsets[blockIdx.x] + block_exclusive_scan((long long)__popc(bits), &total);
+  long long pos = offsets[blockIdx.x] + wave::block_exclusive_scan<BLOCK>((long long)__popc(bits), &total);
 #pragma unroll
   for (int j = 0; j < ITEMS; j++)
     if (bits & (1u << j)) out[pos++] = start + j;

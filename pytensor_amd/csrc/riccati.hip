@@ -28,6 +28,7 @@
 // library's GEMM / LU kernels and ends with pthip_dare_finish, which applies the same convergence test
 // to the last step on the device.
 #include "common.h"
+#include "wave_device.h"
 
 #include <cfloat>
 #include <cmath>
@@ -41,28 +42,19 @@ constexpr int DARE_MAX_STEPS = 48;
 constexpr double DARE_EPS = 2.220446049250313e-16;
 constexpr double DARE_SQRT_EPS = 1.4901161193847656e-08;
 
-// max that propagates NaN (fmax drops it)
-__device__ __forceinline__ double nmax(double a, double b) { return (a != a) ? a : ((b != b) ? b : (a > b ? a : b)); }
-
-__device__ __forceinline__ double wave_max(double v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v = nmax(v, __shfl_xor(v, o));
-  return v;
-}
-
 // block-wide NaN-propagating max of four values at once (every thread gets the results)
 __device__ void block_max4(double (&v)[4], double (*red)[DARE_WAVES]) {
   const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
 #pragma unroll
   for (int q = 0; q < 4; q++) {
-    v[q] = wave_max(v[q]);
+    v[q] = wave::wave_nan_max(v[q]);
     if (lane == 0) red[q][wid] = v[q];
   }
   __syncthreads();
 #pragma unroll
   for (int q = 0; q < 4; q++) {
     v[q] = red[q][0];
-    for (int w = 1; w < DARE_WAVES; w++) v[q] = nmax(v[q], red[q][w]);
+    for (int w = 1; w < DARE_WAVES; w++) v[q] = wave::nan_max(v[q], red[q][w]);
   }
   __syncthreads();
 }
@@ -79,8 +71,8 @@ __device__ void mm(double* C, int ldc, const double* X, int xs0, int xs1, const 
     for (int k = 0; k < K; k++) s = fma(x[k * xs1], y[k * ys0], s);
     const double c = acc ? C[i * ldc + j] + s : s;
     C[i * ldc + j] = c;
-    inc_max = nmax(inc_max, fabs(s));
-    c_max = nmax(c_max, fabs(c));
+    inc_max = wave::nan_max(inc_max, fabs(s));
+    c_max = wave::nan_max(c_max, fabs(c));
   }
 }
 
@@ -195,7 +187,7 @@ __global__ __launch_bounds__(DARE_BLOCK) void dare_sda_kernel(const T* __restric
     const double a = (double)A[e];
     sA[i * ld + j] = a;
     sH[i * ld + j] = (double)Q[e];
-    a0max = nmax(a0max, fabs(a));
+    a0max = wave::nan_max(a0max, fabs(a));
   }
   // G0 = B R^-1 B^T: R -> W, B^T (n x m) -> Y1, B (m x n) -> Y2
   for (int e = tid; e < n * n; e += DARE_BLOCK) sW[(e / n) * ld + e % n] = (double)R[e];
@@ -281,10 +273,10 @@ __global__ __launch_bounds__(DARE_BLOCK) void dare_finish_kernel(const double* _
   const long long mm2 = m * m;
   double hm = 0.0, dm = 0.0, a0 = 0.0, ak = 0.0, z = 0.0;
   for (long long e = threadIdx.x; e < mm2; e += DARE_BLOCK) {
-    hm = nmax(hm, fabs(H[e]));
-    dm = nmax(dm, fabs(dH[e]));
-    a0 = nmax(a0, fabs(A0[e]));
-    ak = nmax(ak, fabs(Ak[e]));
+    hm = wave::nan_max(hm, fabs(H[e]));
+    dm = wave::nan_max(dm, fabs(dH[e]));
+    a0 = wave::nan_max(a0, fabs(A0[e]));
+    ak = wave::nan_max(ak, fabs(Ak[e]));
   }
   double r[4] = {hm, dm, a0, ak};
   block_max4(r, s_red);

@@ -12,6 +12,7 @@
 // (IndexError) and the entry is skipped; row extents are clamped to [0, nnz).  Grids are 1-D and
 // grid-stride, never more than kMaxBlocks workgroups.
 #include "common.h"
+#include "wave_device.h"
 
 namespace {
 
@@ -206,28 +207,6 @@ int spmm_t(long long rows, long long n, long long k, long long nnz, const void* 
 constexpr int SCAN_ITEMS = 8;
 constexpr int SCAN_TILE = BLOCK * SCAN_ITEMS;
 
-__device__ __forceinline__ long long block_exclusive_scan(long long v, long long* total) {
-  __shared__ long long s_wave[BLOCK / 64];
-  const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
-  long long incl = v;
-#pragma unroll
-  for (int o = 1; o < 64; o <<= 1) {
-    const long long t = __shfl_up(incl, o);
-    if (lane >= o) incl += t;
-  }
-  if (lane == 63) s_wave[wid] = incl;
-  __syncthreads();
-  long long base = 0, all = 0;
-#pragma unroll
-  for (int w = 0; w < BLOCK / 64; w++) {
-    if (w < wid) base += s_wave[w];
-    all += s_wave[w];
-  }
-  __syncthreads();
-  *total = all;
-  return base + incl - v;
-}
-
 __global__ __launch_bounds__(BLOCK) void scan_tiles_kernel(const int* __restrict__ in, long long n, long long* __restrict__ sums) {
   const long long start = (long long)blockIdx.x * SCAN_TILE + (long long)threadIdx.x * SCAN_ITEMS;
   long long c = 0;
@@ -235,7 +214,7 @@ __global__ __launch_bounds__(BLOCK) void scan_tiles_kernel(const int* __restrict
   for (int j = 0; j < SCAN_ITEMS; j++)
     if (start + j < n) c += in[start + j];
   long long total;
-  block_exclusive_scan(c, &total);
+  wave::block_exclusive_scan<BLOCK>(c, &total);
   if (threadIdx.x == 0) sums[blockIdx.x] = total;
 }
 
@@ -245,7 +224,7 @@ __global__ __launch_bounds__(BLOCK) void scan_sums_kernel(long long* __restrict_
     const long long i = base + threadIdx.x;
     const long long v = i < nb ? sums[i] : 0;
     long long chunk;
-    const long long ex = block_exclusive_scan(v, &chunk);
+    const long long ex = wave::block_exclusive_scan<BLOCK>(v, &chunk);
     if (i < nb) sums[i] = carry + ex;
     carry += chunk;
   }
@@ -263,7 +242,7 @@ __global__ __launch_bounds__(BLOCK) void scan_apply_kernel(const int* __restrict
     c += v[j];
   }
   long long total;
-  long long pos = sums[blockIdx.x] + block_exclusive_scan(c, &total);
+  long long pos = sums[blockIdx.x] + wave::block_exclusive_scan<BLOCK>(c, &total);
 #pragma unroll
   for (int j = 0; j < SCAN_ITEMS; j++) {
     if (start + j < n) out[start + j] = (int)pos;

@@ -35,20 +35,12 @@
 // Groups never talk to each other: no barriers, no waits; the only atomic is the OR into the error word.  No LDS
 // either, but for one instance (acc_in_lds below).  Every instance builds without scratch (profiles/svd_batched.md).
 #include "common.h"
+#include "wave_device.h"
 
 namespace {
 
 constexpr int WG = 256;  // 4 independent waves
 constexpr int MAX_SWEEPS = 60;
-
-template <class T> __device__ __forceinline__ T dev_abs(T x) { return x < T(0) ? -x : x; }
-
-template <int G, class T>
-__device__ __forceinline__ T group_sum(T y) {
-#pragma unroll
-  for (int o = 1; o < G; o <<= 1) y += __shfl_xor(y, o, 64);
-  return y;
-}
 
 // The float64 instance with 64 rows of 64 and vectors would need row + accumulator = 256 registers before anything is
 // computed: its accumulator lives in LDS instead (acc[k][lane], 32 KiB: own and partner's element are both plain reads,
@@ -142,10 +134,10 @@ __global__ __launch_bounds__((block_size<T, G, NR, VEC>())) void gesvj_wave_kern
         const T pn2 = __shfl(n2, src, 64);
         const bool low = lig < partner;
         const T a = low ? n2 : pn2, b = low ? pn2 : n2;
-        bool rotate = real && g != T(0) && dev_abs(g) > tol * sqrt(a) * sqrt(b);
+        bool rotate = real && g != T(0) && wave::dev_abs(g) > tol * sqrt(a) * sqrt(b);
         const T gs = rotate ? g : T(1);
         const T zeta = (b - a) / (T(2) * gs);
-        const T tt = (zeta >= T(0) ? T(1) : T(-1)) / (dev_abs(zeta) + sqrt(T(1) + zeta * zeta));
+        const T tt = (zeta >= T(0) ? T(1) : T(-1)) / (wave::dev_abs(zeta) + sqrt(T(1) + zeta * zeta));
         rotate = rotate && tt != T(0) && tt == tt;  // (t underflowed: nothing to do, and nothing that counts as a rotation)
         const T cs = T(1) / sqrt(T(1) + tt * tt);
         const T sn = low ? -(cs * tt) : cs * tt;  // p' = c p - s q, q' = s p + c q
@@ -229,7 +221,7 @@ __global__ __launch_bounds__((block_size<T, G, NR, VEC>())) void gesvj_wave_kern
 #pragma unroll
           for (int j = 0; j < NR; j++) {
             if (j < c) {  // (wave-uniform)
-              const T y = group_sum<G>(cf * x[j]);
+              const T y = wave::group_sum<G>(cf * x[j]);
               if (valid && lig == (j & (G - 1))) P[tall ? (long long)k * c + j : (long long)j * r + k] = bad ? nan : y;
             }
           }
@@ -265,7 +257,7 @@ __global__ __launch_bounds__((block_size<T, G, NR, VEC>())) void gesvj_wave_kern
             if (!active) d = T(0);
 #pragma unroll
             for (int j = 0; j < NR; j++) {
-              if (j < c) u[j] -= group_sum<G>(active ? d * x[j] : T(0));
+              if (j < c) u[j] -= wave::group_sum<G>(active ? d * x[j] : T(0));
             }
           }
           T nu = T(0);
