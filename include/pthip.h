@@ -338,6 +338,18 @@ int pthip_convolve1d(int dtype, int64_t na, const void* a, int64_t nb, const voi
  * "valid"): direct sums, a (ha x wa) and b (hb x wb) contiguous */
 int pthip_convolve2d(int dtype, int64_t ha, int64_t wa, const void* a, int64_t hb, int64_t wb, const void* b, int full,
                      void* out);
+/* Blockwise(Convolve1d) / Blockwise(Convolve2d) (csrc/conv_batched.hip): the whole broadcast stack in one launch.
+ * The batch is `nbd` (<= 4) dimensions `bdims`, outermost first, with the element strides `bsa` / `bsb` of the two
+ * operands along them (0 where an operand is shared); `out` is contiguous, (*bdims, *core).  Core operands are read
+ * in place through element strides of either sign (sa, sb; sa0, sa1, sb0, sb1).  The core shapes may come in either
+ * order: the longer (1-d) or larger (2-d) operand is made the first here, once per call, and every output is summed
+ * in increasing index of that operand.  float32 / float64 / int64; "valid" of two matrices of which neither holds the
+ * other is an error. */
+int pthip_convolve1d_batched(int dtype, int nbd, const int64_t* bdims, const int64_t* bsa, const int64_t* bsb, int64_t na,
+                             const void* a, int64_t sa, int64_t nb, const void* b, int64_t sb, int full, void* out);
+int pthip_convolve2d_batched(int dtype, int nbd, const int64_t* bdims, const int64_t* bsa, const int64_t* bsb, int64_t ha,
+                             int64_t wa, const void* a, int64_t sa0, int64_t sa1, int64_t hb, int64_t wb, const void* b,
+                             int64_t sb0, int64_t sb1, int full, void* out);
 
 /* ---- dense decompositions, correct-first tier (csrc/decomp.hip): one workgroup per matrix ---- */
 /* QR.perform (linalg/decomposition/qr.py:153-221): LAPACK geqrf in place on `batch` contiguous

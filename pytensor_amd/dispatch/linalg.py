@@ -210,6 +210,12 @@ def blockwise(node, inputs, env):
 
         if decomp.sylvester_tier(ins[0].shape[-1], ins[1].shape[-1]) == "schur":
             return [decomp.solve_sylvester_schur(env, *ins, bool(cp.get("b_is_a_t", False)), riccati.out_dtype(env, node))]
+    if p["core_op"] in ("Convolve1d", "Convolve2d") and len(ins) == 3:  # (one launch for the whole stack: misc.conv_tier)
+        from pytensor_amd.dispatch import misc
+
+        outs = (misc.convolve1d_stack if p["core_op"] == "Convolve1d" else misc.convolve2d_stack)(node, inputs, env)
+        if outs is not None:
+            return outs
     return _blockwise_loop(node, ins, env, inputs)
 
 

@@ -511,6 +511,117 @@ def convolve2d(node, inputs, env):
     return [out if kdt == dt else _cast(env, out, dt)]
 
 
+# ---- Blockwise(Convolve1d) / Blockwise(Convolve2d): the whole stack in one launch (csrc/conv_batched.hip) ----
+CONV1D_R = 8  # outputs a lane keeps in registers
+CONV1D_TILE = 256 * CONV1D_R  # outputs of one item a workgroup owns; items of <= TILE / 2 (/ 4) outputs go 2 (4) to a workgroup
+CONV1D_CHUNK = 256  # taps staged at a time
+CONV2D_TILE = (16, 64)  # output tile of a workgroup; outputs that fit (32, 16) ... (4, 64) go 2 or 4 items to a workgroup
+CONV2D_ROW_CHUNK = 8  # kernel rows staged at a time (kernels up to CONV2D_COL_CHUNK wide)
+CONV2D_COL_CHUNK = 64  # kernel columns staged at a time, one row at a time, for wider kernels
+CONV_BATCH_DIMS = 4  # batch dimensions the kernels walk by stride; a batch that does not merge into that many is copied
+CONV_STACK_LAUNCHES = 1  # launches of a stack on the one-launch path, plus a copy and a cast per operand (and one cast of the result) whose dtype is promoted
+
+
+def conv_tier(batch_shape, mode_shape=()):
+    """The path a ``Blockwise(Convolve1d)`` / ``Blockwise(Convolve2d)`` node takes, from the shapes alone: "stack" (one
+    launch of csrc/conv_batched.hip for the whole broadcast batch ``batch_shape``, whatever the core shapes) or "loop"
+    (``_blockwise_loop``, one core call per item): a ``full_mode`` operand with batch dimensions of its own
+    (``mode_shape``) and an empty batch.  No shape is sent to the loop for speed: profiles/conv_batched.md."""
+    if len(mode_shape) or any(int(s) == 0 for s in batch_shape):
+        return "loop"
+    return "stack"
+
+
+def _merge_batch(bshape, *stride_sets):
+    """The batch as the fewest (size, strides per operand) dimensions a kernel can walk: length-1 dimensions dropped,
+    neighbours merged where every operand's strides allow it."""
+    dims = []
+    for d, n in enumerate(bshape):
+        if n == 1:
+            continue
+        st = [ss[d] for ss in stride_sets]
+        if dims and all(p == q * n for p, q in zip(dims[-1][1], st)):
+            dims[-1] = (dims[-1][0] * n, st)
+        else:
+            dims.append((n, st))
+    return dims
+
+
+def _conv_stack_operands(env, what, inputs, core_ndim):
+    """(a, b, full, working dtype, result dtype, batch shape, the kernels' batch arguments) of a stacked convolution, or
+    None where the node stays on the per-item loop.  Promotion is that of the unbatched handlers; a host-known ``full_mode`` is read on the host,
+    a device scalar once."""
+    from pytensor_amd.device import _i64arr
+    from pytensor_amd.dispatch.elemwise import _cast
+    from pytensor_amd.dispatch.lu import _batch_strides
+
+    mode = inputs[2]
+    a, b = (env.to_device(i) for i in inputs[:2])
+    if a.ndim < core_ndim or b.ndim < core_ndim:
+        return None
+    bshape = tuple(np.broadcast_shapes(a.shape[: a.ndim - core_ndim], b.shape[: b.ndim - core_ndim]))
+    if conv_tier(bshape, tuple(mode.shape)) != "stack":
+        return None
+    full = bool(np.asarray(env.to_host(mode)).item())
+    dt = np.result_type(np.dtype(a.dtype), np.dtype(b.dtype))
+    if dt.kind == "b":
+        raise NotImplementedError(f"hip linker: {what} of bool arrays")
+    ints = "iub" if core_ndim == 1 else "iu"
+    kdt = dt if dt.name in ("float64", "float32", "int64") else np.dtype("int64" if dt.kind in ints else "float64")
+    a, b = (t if np.dtype(t.dtype) == kdt else _cast(env, t.contiguous(), kdt) for t in (a, b))
+    sets = [_batch_strides(a, core_ndim, bshape), _batch_strides(b, core_ndim, bshape)]
+    dims = _merge_batch(bshape, *sets)
+    if len(dims) > CONV_BATCH_DIMS:
+        from pytensor_amd.dispatch.linalg import _batchify
+
+        a, b = _batchify(a, core_ndim, bshape), _batchify(b, core_ndim, bshape)
+        dims = [(a.shape[0], [a.strides[0], b.strides[0]])]
+    batch = (len(dims), _i64arr([n for n, _ in dims]), _i64arr([st[0] for _, st in dims]), _i64arr([st[1] for _, st in dims]))
+    return a, b, full, kdt, dt, bshape, batch
+
+
+def convolve1d_stack(node, inputs, env):
+    """``Blockwise(Convolve1d)``: np.convolve of every pair of the broadcast stack, one launch; None: not taken"""
+    from pytensor_amd.dispatch.elemwise import _cast
+
+    ops = _conv_stack_operands(env, "Convolve1d", inputs, 1)
+    if ops is None:
+        return None
+    a, b, full, kdt, dt, bshape, batch = ops
+    na, nb = a.shape[-1], b.shape[-1]
+    if na == 0 or nb == 0:
+        raise ValueError("v cannot be empty" if nb == 0 else "a cannot be empty")
+    out = DeviceArray.empty((*bshape, na + nb - 1 if full else abs(na - nb) + 1), kdt)
+    ffi.check(env.lib.pthip_convolve1d_batched(ffi.np_dtype_code(kdt), *batch, na, a.ptr, a.strides[-1], nb, b.ptr, b.strides[-1], int(full), out.ptr))
+    env.keepalive.extend((a, b))
+    return [out if kdt == dt else _cast(env, out, dt)]
+
+
+def convolve2d_stack(node, inputs, env):
+    """``Blockwise(Convolve2d)``: scipy.signal.convolve (direct sums) of every pair of the broadcast stack, one launch;
+    None: not taken"""
+    from pytensor_amd.dispatch.elemwise import _cast
+
+    ops = _conv_stack_operands(env, "Convolve2d", inputs, 2)
+    if ops is None:
+        return None
+    a, b, full, kdt, dt, bshape, batch = ops
+    (ha, wa), (hb, wb) = a.shape[-2:], b.shape[-2:]
+    if 0 in (ha, wa, hb, wb):
+        raise ValueError("convolve2d: empty input")
+    if full:
+        shape = (ha + hb - 1, wa + wb - 1)
+    else:
+        if not ((ha >= hb and wa >= wb) or (hb >= ha and wb >= wa)):
+            raise ValueError("For 'valid' mode, one must be at least as large as the other in every dimension")
+        shape = (abs(ha - hb) + 1, abs(wa - wb) + 1)
+    out = DeviceArray.empty((*bshape, *shape), kdt)
+    ffi.check(env.lib.pthip_convolve2d_batched(ffi.np_dtype_code(kdt), *batch, ha, wa, a.ptr, *a.strides[-2:], hb, wb, b.ptr, *b.strides[-2:],
+                                               int(full), out.ptr))
+    env.keepalive.extend((a, b))
+    return [out if kdt == dt else _cast(env, out, dt)]
+
+
 def _iota(env, n: int) -> DeviceArray:
     out = DeviceArray.empty((n,), "int64")
     if n:

@@ -134,6 +134,8 @@ SIGNATURES = {
     "pthip_searchsorted": (_int, [_int, _i64, _vp, _vp, _int, _i64, _vp, _int, _vp]),
     "pthip_convolve1d": (_int, [_int, _i64, _vp, _i64, _vp, _int, _vp]),
     "pthip_convolve2d": (_int, [_int, _i64, _i64, _vp, _i64, _i64, _vp, _int, _vp]),
+    "pthip_convolve1d_batched": (_int, [_int, _int, C.POINTER(_i64), C.POINTER(_i64), C.POINTER(_i64), _i64, _vp, _i64, _i64, _vp, _i64, _int, _vp]),
+    "pthip_convolve2d_batched": (_int, [_int, _int, C.POINTER(_i64), C.POINTER(_i64), C.POINTER(_i64), _i64, _i64, _vp, _i64, _i64, _i64, _i64, _vp, _i64, _i64, _int, _vp]),
     "pthip_geqrf": (_int, [_int, _i64, _i64, _i64, _vp, _vp]),
     "pthip_geqp3": (_int, [_int, _i64, _i64, _i64, _vp, _vp, _vp]),
     "pthip_orgqr": (_int, [_int, _i64, _i64, _i64, _i64, _vp, _i64, _i64, _vp, _vp]),
