@@ -581,6 +581,30 @@ int pthip_csr_fromdense_fill(int dtype, int64_t rows, int64_t n, const void* x, 
 int pthip_csr_csm_grad(int dtype, int64_t rows, int64_t nnz_x, const void* x_indices, const void* x_indptr, int64_t nnz_g,
                        const void* g_data, const void* g_indices, const void* g_indptr, void* out);
 
+/* ---- sparse x sparse (csrc/spgemm.hip; TrueDot of two sparse operands) ------------------------------------
+ * C = A B for stored CSR matrices A (rows x k) and B (k x n), with the conventions above.  The products of one entry
+ * are added in scipy's order (A's entries of the row in stored order, B's of that row inside each); an entry is kept
+ * iff its value != 0; the indices of every row come out sorted, without duplicates.  The caller reads two totals:
+ *   ws = pthip_spgemm_workspace(dtype, rows, n, dense_tier) bytes, the same buffer for every call of one product
+ *     (dense_tier 0 only if no row can have more than 4096 scalar products: max row of A x max row of B);
+ *   spgemm_structure: indptr_out[rows + 1] of the structural result; indptr_out[rows] = its nnz;
+ *   spgemm_values: indices / data (that nnz) filled at indptr_s, indptr_out[rows + 1] of the entries != 0;
+ *   spgemm_compact (only if indptr_out[rows] differs from the structural nnz): the entries != 0 of indices / data,
+ *     rows at indptr_s, copied in order to indices_out / data_out, rows at indptr.
+ * spgemm_dense: out[i, j] (strides so0, so1) += (A B)[i, j], same order of additions; needs only the workspace. */
+size_t pthip_spgemm_workspace(int dtype, int64_t rows, int64_t n, int dense_tier);
+int pthip_spgemm_structure(int dtype, int64_t rows, int64_t k, int64_t n, int64_t nnz_a, const void* a_indices,
+                           const void* a_indptr, int64_t nnz_b, const void* b_indices, const void* b_indptr, void* ws,
+                           size_t ws_bytes, void* indptr_out);
+int pthip_spgemm_values(int dtype, int64_t rows, int64_t k, int64_t n, int64_t nnz_a, const void* a_data, const void* a_indices,
+                        const void* a_indptr, int64_t nnz_b, const void* b_data, const void* b_indices, const void* b_indptr,
+                        void* ws, size_t ws_bytes, const void* indptr_s, void* indices, void* data, void* indptr_out);
+int pthip_spgemm_compact(int dtype, int64_t rows, const void* indptr_s, const void* indices, const void* data,
+                         const void* indptr, void* indices_out, void* data_out);
+int pthip_spgemm_dense(int dtype, int64_t rows, int64_t k, int64_t n, int64_t nnz_a, const void* a_data, const void* a_indices,
+                       const void* a_indptr, int64_t nnz_b, const void* b_data, const void* b_indices, const void* b_indptr,
+                       void* ws, size_t ws_bytes, void* out, int64_t so0, int64_t so1);
+
 /* ---- Discrete algebraic Riccati equation (csrc/riccati.hip; SolveDiscreteARE, linalg/solvers/linear_control.py) ----
  * dare: X (batch, m, m) = the stabilising solution of A^T X A - X - A^T X B (R + B^T X B)^-1 B^T X A + Q = 0 for
  *   contiguous A (batch, m, m), B (batch, m, n), Q (batch, m, m), R (batch, n, n), by the doubling algorithm, one

@@ -12,6 +12,7 @@
 // (IndexError) and the entry is skipped; row extents are clamped to [0, nnz).  Grids are 1-D and
 // grid-stride, never more than kMaxBlocks workgroups.
 #include "common.h"
+#include "csr_device.h"
 #include "wave_device.h"
 
 namespace {
@@ -27,14 +28,7 @@ inline unsigned grid_for(long long work, int per_block) {
   return (unsigned)b;
 }
 
-__device__ __forceinline__ void row_extent(const int* __restrict__ indptr, long long r, long long nnz, long long* lo,
-                                           long long* hi) {
-  long long a = indptr[r], b = indptr[r + 1];
-  a = a < 0 ? 0 : (a > nnz ? nnz : a);
-  b = b < a ? a : (b > nnz ? nnz : b);
-  *lo = a;
-  *hi = b;
-}
+using csr::row_extent;
 
 // row owning entry e: the last r with indptr[r] <= e (rows of zero length are skipped); -1 if none
 __device__ __forceinline__ long long row_of(const int* __restrict__ indptr, long long rows, long long e) {

@@ -1,4 +1,4 @@
-"""pytensor.sparse csr / csc matrices (csrc/sparse.hip).
+"""pytensor.sparse csr / csc matrices (csrc/sparse.hip; sparse x sparse products: csrc/spgemm.hip).
 
 A sparse value is a :class:`~pytensor_amd.device.DeviceSparse`: the three CSR arrays of the matrix (csr) or of
 its transpose (csc — scipy's csc arrays are exactly those), so every kernel works on one stored CSR matrix
@@ -20,6 +20,9 @@ from pytensor_amd.dispatch import handler
 from pytensor_amd.executor import HostValue
 
 _LONG_ROW = 1024  # csrc/sparse.hip kLongRow
+SPGEMM_WAVE_UB = 256  # csrc/spgemm.hip kWaveUb: the most scalar products of a row in the wave tier
+SPGEMM_WG_UB = 4096  # csrc/spgemm.hip kWgUb: ... in the workgroup tier; beyond it the dense-row tier
+SPGEMM_PIECE = {"wave": 64, "workgroup": 256}  # entries of A's row per LDS prefix array (the group's lanes)
 
 
 def _code(dt):
@@ -233,9 +236,59 @@ def sparse_dot(node, inputs, env):
     return [dense_times_sparse(env, x, y)]
 
 
+def _host_total(env, ptr: DeviceArray, rows) -> int:
+    """ptr[rows] of an int32 prefix array: a 4-byte host read (inside a capture it raises, and the graph stays eager)"""
+    total = int(np.asarray(env.to_host(ptr.view((1,), (1,), rows)))[0])
+    if total < 0:
+        raise ValueError("hip linker: sparse product: the result has more than 2**31 - 1 entries")
+    return total
+
+
+def spgemm(env, a: DeviceSparse, b: DeviceSparse):
+    """(data, indices, indptr) of the CSR of A·B, A and B the *stored* CSR matrices of ``a`` and ``b``
+    (csrc/spgemm.hip: bound and bin, structure, values, and a compaction when a computed value is exactly 0)"""
+    rows, k, n = a.major, a.minor, b.minor
+    code = _code(a.dtype)
+    if rows == 0 or n == 0 or a.nnz == 0 or b.nnz == 0:
+        ptr = DeviceArray.empty((rows + 1,), "int32")
+        ffi.check(env.lib.pthip_memset(ptr.ptr, 0, ptr.nbytes))
+        return DeviceArray.empty((0,), a.dtype), DeviceArray.empty((0,), "int32"), ptr
+    # no row can reach the dense-row tier when the longest rows say so (known for inputs and constants)
+    dense_tier = a.max_row is None or b.max_row is None or a.max_row * b.max_row > SPGEMM_WG_UB
+    ws_bytes = env.lib.pthip_spgemm_workspace(code, rows, n, int(dense_tier))
+    ws = DeviceArray.empty((ws_bytes,), "uint8")
+    a_arrays = (a.nnz, a.data.ptr, a.indices.ptr, a.indptr.ptr)
+    b_arrays = (b.nnz, b.data.ptr, b.indices.ptr, b.indptr.ptr)
+    ptr_s = DeviceArray.empty((rows + 1,), "int32")
+    ffi.check(env.lib.pthip_spgemm_structure(code, rows, k, n, a.nnz, a.indices.ptr, a.indptr.ptr, b.nnz, b.indices.ptr,
+                                             b.indptr.ptr, ws.ptr, ws_bytes, ptr_s.ptr))
+    nnz_s = _host_total(env, ptr_s, rows)  # host read 1: the structural nnz
+    data, ind = DeviceArray.empty((nnz_s,), a.dtype), DeviceArray.empty((nnz_s,), "int32")
+    ptr = DeviceArray.empty((rows + 1,), "int32")
+    ffi.check(env.lib.pthip_spgemm_values(code, rows, k, n, *a_arrays, *b_arrays, ws.ptr, ws_bytes, ptr_s.ptr, ind.ptr, data.ptr,
+                                          ptr.ptr))
+    nnz = _host_total(env, ptr, rows)  # host read 2: the entries != 0
+    if nnz == nnz_s:
+        return data, ind, ptr_s
+    data_c, ind_c = DeviceArray.empty((nnz,), a.dtype), DeviceArray.empty((nnz,), "int32")
+    ffi.check(env.lib.pthip_spgemm_compact(code, rows, ptr_s.ptr, ind.ptr, data.ptr, ptr.ptr, ind_c.ptr, data_c.ptr))
+    return data_c, ind_c, ptr
+
+
 @handler("TrueDot")
 def true_dot(node, inputs, env):
     x, y = inputs
+    if isinstance(y, DeviceSparse):
+        # sparse x sparse, the result in x's format (TrueDot.perform).  With S(.) the stored CSR (of the transpose
+        # for csc): a csr result is S(x) S(y), a csc result is stored as (x y)^T = S(y) S(x).
+        _require_dtype(node, x, y)
+        _check(x.shape[1] == y.shape[0], node, f"shapes {x.shape} and {y.shape} not aligned")
+        if x.format == "csr":
+            a, b = x, _csr_of(env, y, False)
+        else:
+            a, b = _csr_of(env, y, True), x
+        data, ind, ptr = spgemm(env, a, b)
+        return [DeviceSparse(data, ind, ptr, (x.shape[0], y.shape[1]), x.format)]
     y = _dev(env, y)
     _require_dtype(node, x, y)
     d = sparse_times_dense(env, x, y)

@@ -192,6 +192,11 @@ SIGNATURES = {
     "pthip_csr_fromdense_count": (_int, [_int, _i64, _i64, _vp, _i64, _i64, _vp]),
     "pthip_csr_fromdense_fill": (_int, [_int, _i64, _i64, _vp, _i64, _i64, _vp, _vp, _vp]),
     "pthip_csr_csm_grad": (_int, [_int, _i64, _i64, _vp, _vp, _i64, _vp, _vp, _vp, _vp]),
+    "pthip_spgemm_workspace": (_sz, [_int, _i64, _i64, _int]),
+    "pthip_spgemm_structure": (_int, [_int, _i64, _i64, _i64, _i64, _vp, _vp, _i64, _vp, _vp, _vp, _sz, _vp]),
+    "pthip_spgemm_values": (_int, [_int, _i64, _i64, _i64, _i64, _vp, _vp, _vp, _i64, _vp, _vp, _vp, _vp, _sz, _vp, _vp, _vp, _vp]),
+    "pthip_spgemm_compact": (_int, [_int, _i64, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "pthip_spgemm_dense": (_int, [_int, _i64, _i64, _i64, _i64, _vp, _vp, _vp, _i64, _vp, _vp, _vp, _vp, _sz, _vp, _i64, _i64]),
     "pthip_set_safe_mode": (_int, [_int]),
 }
 

@@ -840,7 +840,7 @@ def _register_sparse():
 
     @hip_funcify.register(sm.TrueDot)
     def _(op, node, ctx):
-        _dense_and_sparse(op, node)
+        # (two sparse operands: the SpGEMM of csrc/spgemm.hip)
         if node is not None and not _is_sparse(node.inputs[0]):
             raise NotImplementedError("hip linker: TrueDot with a dense left operand is not lowered")
         return "TrueDot", {}

@@ -7,7 +7,9 @@ the 256 MiB Infinity Cache serves nothing; the reported time is the mean over th
 the whole rotation, no host sync inside).  Roofline in algorithmic bytes:
   SpMV / SpMM: nnz*(sizeof(dtype)+4) + (m+1)*4 + n*k*sizeof(dtype) (B, gathered at least once) + m*k*sizeof(dtype)
   transpose:   2 * nnz*(sizeof(dtype)+4) + (m+1)*4 + (n+1)*4
-fraction = bytes / time / 8 TB/s.  One JSON line per case.   usage: python tools/bench_sparse.py [--quick]
+fraction = bytes / time / 8 TB/s.  SpGEMM (csrc/spgemm.hip): A @ A for the 1e6 Laplacian and A @ A.T for the power-law
+matrix, the whole product with its two host reads, against scipy's A @ B.  One JSON line per case.
+usage: python tools/bench_sparse.py [--quick] [--spgemm: only the SpGEMM rows]
 """
 import ctypes as C
 import json
@@ -121,6 +123,69 @@ def bench_matrix(lib, name, A):
                       "GB/s": round(per / ms / 1e6, 1), "frac_8TBs": round(per / (ms * 1e-3) / HBM, 3), "equals_tocsc": ok}), flush=True)
 
 
+class _Env:
+    """what dispatch/sparse.py::spgemm asks of the executor's environment: the library and the small host reads"""
+
+    def __init__(self, lib):
+        self.lib = lib
+
+    @staticmethod
+    def to_host(v):
+        return v.to_host()
+
+
+def bench_spgemm(lib, name, A, B):
+    """C = A @ B as true_dot computes it (csrc/spgemm.hip through dispatch/sparse.py::spgemm: bound and bin, structure,
+    values, two 4-byte host reads), cold, wall clock over the rotation; scipy's A @ B on the same box next to it."""
+    from pytensor_amd.device import DeviceSparse
+    from pytensor_amd.dispatch.sparse import spgemm
+
+    env = _Env(lib)
+    t0 = time.perf_counter()
+    want = A @ B
+    scipy_ms = (time.perf_counter() - t0) * 1e3
+    want.sort_indices()
+    per = (A.nnz + B.nnz + want.nnz) * 12 + (2 * A.shape[0] + B.shape[0] + 3) * 4
+    copies = max(2, min(16, int(np.ceil(ROTATE / per))))
+    sets = [(DeviceSparse.from_host(A), DeviceSparse.from_host(B)) for _ in range(copies)]
+    data, ind, ptr = spgemm(env, *sets[0])  # warm: code loaded, pool filled
+    ok = bool(np.array_equal(ptr.to_host(), want.indptr) and np.array_equal(ind.to_host(), want.indices))
+    got = data.to_host()
+    err = float(np.max(np.abs(got - want.data)) / np.max(np.abs(want.data))) if ok else float("nan")
+    del data, ind, ptr, got
+    ffi.check(lib.pthip_synchronize())
+    t0 = time.perf_counter()
+    for a, b in sets:
+        spgemm(env, a, b)
+    ffi.check(lib.pthip_synchronize())
+    ms = (time.perf_counter() - t0) * 1e3 / copies
+    print(json.dumps({"case": "spgemm", "matrix": name, "rows": A.shape[0], "nnz_a": A.nnz, "nnz_b": B.nnz, "nnz_c": want.nnz,
+                      "copies": copies, "ms": round(ms, 2), "scipy_ms": round(scipy_ms, 1), "speedup": round(scipy_ms / ms, 1),
+                      "GB/s": round(per / ms / 1e6, 1), "structure_equals_scipy": ok, "relerr": err}), flush=True)
+
+
+def bench_spgemm_dense(lib, side=64):
+    """the dense_out mode of the value pass (pthip_spgemm_dense): A @ A of a small Laplacian added into a dense array"""
+    A = laplacian(side)
+    m = A.shape[0]
+    d, i, p = upload(A)
+    ws_bytes = lib.pthip_spgemm_workspace(7, m, m, 0)
+    ws = DeviceArray.empty((ws_bytes,), "uint8")
+    out = DeviceArray.empty((m, m), "float64")
+
+    def run():
+        ffi.check(lib.pthip_memset(out.ptr, 0, out.nbytes))
+        ffi.check(lib.pthip_spgemm_dense(7, m, m, m, A.nnz, d.ptr, i.ptr, p.ptr, A.nnz, d.ptr, i.ptr, p.ptr, ws.ptr, ws_bytes, out.ptr, m, 1))
+
+    ms = timed(lib, [run])
+    t0 = time.perf_counter()
+    want = (A @ A).toarray()
+    scipy_ms = (time.perf_counter() - t0) * 1e3
+    print(json.dumps({"case": "spgemm dense_out (zero fill included)", "matrix": f"laplacian_{m}", "rows": m, "nnz_a": A.nnz,
+                      "us": round(ms * 1e3, 1), "scipy_toarray_ms": round(scipy_ms, 1), "equals_scipy": bool(np.array_equal(out.to_host(), want))}),
+          flush=True)
+
+
 def bench_car(side, reps):
     import e2e_util as E
 
@@ -152,7 +217,16 @@ def main():
     if not quick:
         mats.insert(1, ("laplacian_1e7", lambda: laplacian(3163)))
     for name, make in mats:
-        bench_matrix(lib, name, make())
+        A = make()
+        if "--spgemm" not in sys.argv:
+            bench_matrix(lib, name, A)
+        if name == "laplacian_1e6":
+            bench_spgemm(lib, f"{name} A @ A", A, A)
+        if name == "power_law_1e6":
+            bench_spgemm(lib, f"{name} A @ A.T", A, A.T.tocsr())
+    bench_spgemm_dense(lib)
+    if "--spgemm" in sys.argv:
+        return
     bench_car(1000, 20 if quick else 50)
 
 
