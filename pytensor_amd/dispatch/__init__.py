@@ -18,4 +18,19 @@ def handler(*names):
     return deco
 
 
+# Core ops that take a whole ``Blockwise`` stack in one call: core op name → ``stack(node, ins, raw, env) -> outputs | None``.
+# ``node`` is the Blockwise node (the core op's params under ``node.params["core_params"]``), ``ins`` its operands on the
+# device, ``raw`` the operands as given; None: not taken at these shapes, the per-item loop runs (linalg.blockwise).
+STACKED = {}
+
+
+def stacked(*core_ops):
+    def deco(f):
+        for n in core_ops:
+            STACKED[n] = f
+        return f
+
+    return deco
+
+
 from pytensor_amd.dispatch import basic, blas, decomp, dotew, elemwise, extra, fft, fused, linalg, lu, misc, random, riccati, scan, sparse, subtensor, tail, wide  # noqa: E402,F401

@@ -19,18 +19,10 @@ import numpy as np
 
 from pytensor_amd import ffi
 from pytensor_amd.device import DeviceArray, contiguous_strides, copy_into
-from pytensor_amd.dispatch import handler
-from pytensor_amd.dispatch.linalg import _dt, _require_float
+from pytensor_amd.dispatch import handler, stacked
+from pytensor_amd.dispatch.batch import as_contiguous, batch_strides, batchify, collapse_batch, swap_core, walk_outer
+from pytensor_amd.dispatch.linalg import _dt, _lapack_operands, _require_float
 from pytensor_amd.executor import HostValue
-
-
-def _cs(shape):
-    return contiguous_strides(tuple(shape))
-
-
-def _reshape(x: DeviceArray, shape) -> DeviceArray:
-    x = x.contiguous()
-    return x.view(tuple(shape), _cs(shape))
 
 
 def _t(x: DeviceArray) -> DeviceArray:
@@ -39,8 +31,6 @@ def _t(x: DeviceArray) -> DeviceArray:
 
 
 def _matrix(env, v, what):
-    from pytensor_amd.dispatch.linalg import _lapack_operands
-
     (x,) = _lapack_operands(env, what, v)
     if x.ndim != 2:
         # (np.linalg raises LinAlgError: "%d-dimensional array given. Array must be two-dimensional")
@@ -115,15 +105,12 @@ def _geqp3_empty(m: int, n: int, dtype) -> None:
     geqp3(a, lwork=work.item())
 
 
-@handler("QR")
-def qr_op(node, inputs, env):
+def qr_device(env, x, params):
     """``QR.perform``.  The operand may carry leading batch dimensions (``Blockwise`` hands the whole stack over:
     every kernel takes a batch count); with ``pivoting`` (geqp3) the permutation is the last output."""
-    from pytensor_amd.dispatch.linalg import _lapack_operands
-
-    mode = node.params["mode"]
-    pivoting = bool(node.params.get("pivoting", False))
-    (x,) = _lapack_operands(env, "QR", inputs[0])
+    mode = params["mode"]
+    pivoting = bool(params.get("pivoting", False))
+    (x,) = _lapack_operands(env, "QR", x)
     if x.ndim < 2:
         raise np.linalg.LinAlgError(f"QR: {x.ndim}-dimensional array given. Array must be at least two-dimensional")
     m, n = x.shape[-2:]
@@ -148,6 +135,16 @@ def qr_op(node, inputs, env):
     else:
         Q = orgqr_device(env, qr, tau, m)
     return [Q, R, *P]
+
+
+@handler("QR")
+def qr_op(node, inputs, env):
+    return qr_device(env, inputs[0], node.params)
+
+
+@stacked("QR")
+def qr_stack(node, ins, raw, env):
+    return qr_device(env, ins[0], node.params["core_params"])
 
 
 # ---- SVD ------------------------------------------------------------------------------------------
@@ -188,7 +185,7 @@ def svd_device(env, x: DeviceArray, full_matrices: bool, compute_uv: bool):
         big = Wt
     else:
         big = DeviceArray.empty((rows, c), dt)
-        copy_into(big.view((r, c), _cs((r, c))), Wt)
+        copy_into(big.view((r, c), contiguous_strides((r, c))), Wt)
     ffi.check(env.lib.pthip_fill_null_rows(_dt(x), 1, rows, c, big.ptr, S.ptr, r, Q.ptr, rows))
     env.keepalive.extend((Q, qr, tau))
     if tall:  # x^T = P S Wt  ->  x = Wt^T S P^T
@@ -222,7 +219,7 @@ def _svd_block(env, x: DeviceArray, full_matrices: bool, compute_uv: bool):
     *lead, m, n = x.shape
     nb = int(np.prod(lead)) if lead else 1
     tall = m >= n
-    X = (_tb(x) if tall else x).contiguous_copy()  # (..., r, c), r <= c
+    X = (swap_core(x) if tall else x).contiguous_copy()  # (..., r, c), r <= c
     r, c = X.shape[-2:]
     dt = x.dtype
     S = DeviceArray.empty((*lead, r), dt)
@@ -236,21 +233,14 @@ def _svd_block(env, x: DeviceArray, full_matrices: bool, compute_uv: bool):
     ffi.check(env.lib.pthip_svd_block(_dt(x), nb, r, c, 1, rows, X.ptr, S.ptr, Wt.ptr, Pt.ptr))
     env.keepalive.append(X)
     if tall:  # x^T = P S Wt  ->  x = Wt^T S P^T
-        return [_tb(Wt).contiguous(), S, Pt]
-    return [_tb(Pt).contiguous(), S, Wt]
-
-
-def _tb(x: DeviceArray) -> DeviceArray:
-    """the stack with its two core dimensions swapped (a view)"""
-    return x.view((*x.shape[:-2], x.shape[-1], x.shape[-2]), (*x.strides[:-2], x.strides[-1], x.strides[-2]))
+        return [swap_core(Wt).contiguous(), S, Pt]
+    return [swap_core(Pt).contiguous(), S, Wt]
 
 
 def gesvj_device(env, x: DeviceArray, job: int, rcond: float = 0.0):
     """``pthip_gesvj_batched`` on a stack (..., m, n) of the wave tier.  job 0: [S]; 1 / 2: [U, S, Vt] economic / full;
     3: [pinv].  Leading dimensions reach the kernel as one batch stride where they fold (a broadcast or strided stack
     included: nothing is copied); the dimensions that do not fold are walked here, one launch per outer index."""
-    from pytensor_amd.dispatch.lu import _batch_strides, _collapse_batch
-
     *lead, m, n = x.shape
     lead = tuple(lead)
     k, dt = min(m, n), x.dtype
@@ -264,9 +254,8 @@ def gesvj_device(env, x: DeviceArray, job: int, rcond: float = 0.0):
         outs = [U, S, Vt] if job else [S]
         slots = [U, S, Vt, None]
     per = [0 if o is None else int(np.prod(o.shape[len(lead):])) * o.itemsize for o in slots]
-    outer, inner, st = _collapse_batch(lead, _batch_strides(x, 2, lead))
-    for f, idx in enumerate(np.ndindex(*[s for s, _ in outer])):
-        off = sum(i * sts[0] for i, (_, sts) in zip(idx, outer))
+    outer, inner, st = collapse_batch(lead, batch_strides(x, 2, lead))
+    for f, (off,) in walk_outer(outer, 1):
         ptrs = [None if o is None else o.ptr + f * inner * p for o, p in zip(slots, per)]
         ffi.check(env.lib.pthip_gesvj_batched(_dt(x), inner, m, n, job, x.ptr + off * x.itemsize, st[0], x.strides[-2], x.strides[-1],
                                               float(rcond), *ptrs))
@@ -296,7 +285,7 @@ def _svd_stack(env, x: DeviceArray, full_matrices: bool, compute_uv: bool):
     if tier == "block":
         return _svd_block(env, x, full_matrices, compute_uv)
     tall = m >= n
-    X = (_tb(x) if tall else x).contiguous_copy()  # (..., r, c), r <= c
+    X = (swap_core(x) if tall else x).contiguous_copy()  # (..., r, c), r <= c
     r, c = X.shape[-2:]
     S = DeviceArray.empty((*lead, r), dt)
     work = DeviceArray.empty((nb, r, r), dt) if compute_uv else DeviceArray.empty((1,), dt)
@@ -307,7 +296,7 @@ def _svd_stack(env, x: DeviceArray, full_matrices: bool, compute_uv: bool):
     if not compute_uv:
         return [S]
     rows = c if full_matrices else r
-    qr, tau = geqrf_device(env, _tb(Wt))
+    qr, tau = geqrf_device(env, swap_core(Wt))
     Q = orgqr_device(env, qr, tau, rows)
     if rows == r:
         big = Wt
@@ -317,29 +306,33 @@ def _svd_stack(env, x: DeviceArray, full_matrices: bool, compute_uv: bool):
     ffi.check(env.lib.pthip_fill_null_rows(_dt(x), nb, rows, c, big.ptr, S.ptr, r, Q.ptr, rows))
     env.keepalive.extend((Q, qr, tau))
     if tall:  # x^T = P S Wt  ->  x = Wt^T S P^T
-        return [_tb(big).contiguous(), S, Pt]
-    return [_tb(Pt).contiguous(), S, big]
+        return [swap_core(big).contiguous(), S, Pt]
+    return [swap_core(Pt).contiguous(), S, big]
 
 
 def _stack_operand(env, v, what):
-    from pytensor_amd.dispatch.linalg import _lapack_operands
-
     (x,) = _lapack_operands(env, what, v)
     if x.ndim < 2:
         raise np.linalg.LinAlgError(f"{what}: {x.ndim}-dimensional array given. Array must be at least two-dimensional")
     return x
 
 
-def svd_stack_op(node, inputs, env):
+@stacked("SVD")
+def svd_stack_op(node, ins, raw, env):
     """``Blockwise(SVD)``: the whole stack in one call"""
-    x = _stack_operand(env, inputs[0], "SVD")
-    return svd_device(env, x, bool(node.params["full_matrices"]), bool(node.params["compute_uv"]))
+    cp = node.params["core_params"]
+    x = _stack_operand(env, ins[0], "SVD")
+    return svd_device(env, x, bool(cp["full_matrices"]), bool(cp["compute_uv"]))
 
 
-def pinv_stack_op(node, inputs, env):
-    """``Blockwise(MatrixPinv)``: job 3 of the wave tier in one launch; above it the batched SVD, the cut-off as one
-    elementwise launch and two batched GEMMs"""
-    x = _stack_operand(env, inputs[0], "MatrixPinv")
+@stacked("MatrixPinv")
+def pinv_stack_op(node, ins, raw, env):
+    return pinv_device(env, _stack_operand(env, ins[0], "MatrixPinv"))
+
+
+def pinv_device(env, x: DeviceArray):
+    """``np.linalg.pinv`` of a matrix or a stack.  A matrix: its SVD, the cut-off and two GEMMs.  A stack: job 3 of the
+    wave tier in one launch; above it the batched SVD, the cut-off as one elementwise launch and two batched GEMMs"""
     *lead, m, n = x.shape
     nb = int(np.prod(lead)) if lead else 1
     if nb == 0 or m == 0 or n == 0:
@@ -363,7 +356,7 @@ def _pinv_apply_stack(env, U, S, Vt, rcond_dev):
     n = Vt.shape[-1]
     nb = int(np.prod(lead)) if lead else 1
     dt = str(S.dtype)
-    U, S, Vt = (_reshape(a, (nb, *a.shape[len(lead):])) for a in (U, S, Vt))
+    U, S, Vt = (as_contiguous(a, (nb, *a.shape[len(lead):])) for a in (U, S, Vt))
     body = {"in_dtypes": [dt, dt, dt], "out_dtypes": [dt],
             "body": [{"op": "Mul", "in": [["i", 1], ["i", 2]], "dtype": dt},
                      {"op": "GT", "in": [["i", 0], ["t", 0]], "dtype": "bool"},
@@ -375,7 +368,7 @@ def _pinv_apply_stack(env, U, S, Vt, rcond_dev):
     Ut = U.view((nb, k, m), (m * k, 1, k))
     (scaled,), _, _ = launch_elemwise(scale, [Ut, sinv.view((nb, k, m), (k, 1, 0))], (nb, k, m), [dt], None, env)
     out = gemm_device(env, 1.0, Vt.view((nb, n, k), (k * n, 1, n)), scaled, batch=True)
-    return out.view((*lead, n, m), _cs((*lead, n, m)))
+    return out.view((*lead, n, m), contiguous_strides((*lead, n, m)))
 
 
 @handler("SVD")
@@ -409,13 +402,7 @@ def _pinv_apply(env, U, S, Vt, rcond_dev, rhs=None):
 
 @handler("MatrixPinv")
 def matrix_pinv(node, inputs, env):
-    x = _matrix(env, inputs[0], "MatrixPinv")
-    m, n = x.shape
-    if m == 0 or n == 0:
-        return [DeviceArray.empty((n, m), x.dtype)]
-    U, S, Vt = svd_device(env, x, False, True)
-    rcond = env.to_device(HostValue(np.asarray([1e-15], dtype=x.dtype)))  # np.linalg.pinv's default
-    return [_pinv_apply(env, U, S, Vt, rcond)]
+    return pinv_device(env, _matrix(env, inputs[0], "MatrixPinv"))
 
 
 @handler("Lstsq")
@@ -490,21 +477,15 @@ def gttrs_device(env, dl, d, du, du2, ipiv, b, transposed):
     return out
 
 
-def _same_float(env, vals, what):
-    from pytensor_amd.dispatch.linalg import _lapack_operands
-
-    return _lapack_operands(env, what, *vals)
-
-
 @handler("LUFactorTridiagonal")
 def lu_factor_tridiagonal(node, inputs, env):
-    dl, d, du = _same_float(env, inputs, "LUFactorTridiagonal")
+    dl, d, du = _lapack_operands(env, "LUFactorTridiagonal", *inputs)
     return list(gttrf_device(env, dl, d, du))
 
 
 @handler("SolveLUFactorTridiagonal")
 def solve_lu_factor_tridiagonal(node, inputs, env):
-    dl, d, du, du2, b = _same_float(env, [inputs[0], inputs[1], inputs[2], inputs[3], inputs[5]], "SolveLUFactorTridiagonal")
+    dl, d, du, du2, b = _lapack_operands(env, "SolveLUFactorTridiagonal", *inputs[:4], inputs[5])
     ipiv = env.to_device(inputs[4])
     if str(ipiv.dtype) != "int32":
         from pytensor_amd.dispatch.elemwise import _cast
@@ -520,12 +501,9 @@ def solve_tridiagonal(env, A: DeviceArray, b: DeviceArray, b_ndim: int) -> Devic
     if A.ndim != 2 or b.ndim != b_ndim:
         # batched (Blockwise; reference tests/tensor/rewriting/linalg/test_solvers.py): the (small) batch on the host, like
         # dispatch/lu.solve_general — each item is a factorisation and a solve launch
-        from pytensor_amd.device import contiguous_strides, copy_into
-        from pytensor_amd.dispatch.lu import _batchify
-
         bshape = tuple(np.broadcast_shapes(A.shape[:-2], b.shape[: b.ndim - b_ndim]))
         core_b = b.shape[b.ndim - b_ndim:]
-        Ab, bbm = _batchify(A, 2, bshape), _batchify(b, b_ndim, bshape)
+        Ab, bbm = batchify(A, 2, bshape), batchify(b, b_ndim, bshape)
         out = DeviceArray.empty((*bshape, *core_b), b.dtype)
         step = int(np.prod(core_b)) if core_b else 1
         for k in range(Ab.shape[0]):
@@ -540,16 +518,15 @@ def solve_tridiagonal(env, A: DeviceArray, b: DeviceArray, b_ndim: int) -> Devic
 # ---- composed from existing device ops ----------------------------------------------------------------
 @handler("Eigvalsh")
 def eigvalsh(node, inputs, env):
-    from pytensor_amd.dispatch.lu import eigh
+    from pytensor_amd.dispatch.lu import eigh_device
 
     ins = [i for i in inputs if not (isinstance(i, HostValue) and i.a.dtype == object)]
-    fake = type("_N", (), {"params": {"lower": bool(node.params["lower"])}})
-    return [eigh(fake, ins, env)[0]]
+    return [eigh_device(env, ins, bool(node.params["lower"]))[0]]
 
 
 @handler("TensorInv")
 def tensor_inv(node, inputs, env):
-    from pytensor_amd.dispatch.lu import matrix_inverse
+    from pytensor_amd.dispatch.lu import matrix_inverse_device
 
     a = env.to_device(inputs[0])
     ind = int(node.params["ind"])
@@ -558,19 +535,18 @@ def tensor_inv(node, inputs, env):
     old = tuple(a.shape)
     inv_shape = old[ind:] + old[:ind]
     prod = int(np.prod(old[ind:])) if old[ind:] else 1
-    a2 = _reshape(a, (prod, a.size // prod if prod else 0))
+    a2 = as_contiguous(a, (prod, a.size // prod if prod else 0))
     if a2.shape[0] != a2.shape[1]:
         raise np.linalg.LinAlgError("Last 2 dimensions of the array must be square")
-    fake = type("_N", (), {"params": {}})
-    (ia,) = matrix_inverse(fake, [a2], env)
-    return [_reshape(ia, inv_shape)]
+    ia = matrix_inverse_device(env, a2)
+    return [as_contiguous(ia, inv_shape)]
 
 
 @handler("TensorSolve")
 def tensor_solve(node, inputs, env):
     from pytensor_amd.dispatch.lu import solve_general
 
-    a, b = _same_float(env, inputs, "TensorSolve")
+    a, b = _lapack_operands(env, "TensorSolve", *inputs)
     axes = node.params.get("axes")
     an = a.ndim
     if axes is not None:
@@ -583,8 +559,8 @@ def tensor_solve(node, inputs, env):
     prod = int(np.prod(old)) if old else 1
     if a.size != prod * prod:
         raise np.linalg.LinAlgError("Input arrays must satisfy the requirement prod(a.shape[b.ndim:]) == prod(a.shape[:b.ndim])")
-    x = solve_general(env, _reshape(a, (prod, prod)), _reshape(b, (prod,)), 1)
-    return [_reshape(x, old)]
+    x = solve_general(env, as_contiguous(a, (prod, prod)), as_contiguous(b, (prod,)), 1)
+    return [as_contiguous(x, old)]
 
 
 @handler("BlockDiagonal")
@@ -707,8 +683,6 @@ def solve_sylvester_schur(env, A, B, C, b_is_a_t=False, out_dtype=None):
     No host read."""
     from pytensor_amd.dispatch.blas import gemm_device
     from pytensor_amd.dispatch.elemwise import _cast
-    from pytensor_amd.dispatch.linalg import _batchify, _lapack_operands
-
     A, B, C = _lapack_operands(env, "SolveSylvester", A, B, C)
     m, n = A.shape[-1], B.shape[-1]
     if A.shape[-2:] != (m, m) or B.shape[-2:] != (n, n) or C.shape[-2:] != (m, n):
@@ -723,9 +697,9 @@ def solve_sylvester_schur(env, A, B, C, b_is_a_t=False, out_dtype=None):
     if max(m, n) > MAX_SYLVESTER_SCHUR:
         raise _sylvester_refused(m, n)
     f64 = "float64"
-    Ab = _batchify(A, 2, bshape)
-    Bb = None if b_is_a_t else _batchify(B, 2, bshape)
-    Cb = _batchify(C, 2, bshape)
+    Ab = batchify(A, 2, bshape)
+    Bb = None if b_is_a_t else batchify(B, 2, bshape)
+    Cb = batchify(C, 2, bshape)
     if str(Cb.dtype) != f64:
         Cb = _cast(env, Cb, f64)
     ws_bytes = int(env.lib.pthip_sylvester_workspace(nb, m, n, int(b_is_a_t)))
@@ -745,6 +719,16 @@ def solve_sylvester_schur(env, A, B, C, b_is_a_t=False, out_dtype=None):
     return X.view(out.shape, contiguous_strides(out.shape))
 
 
+@stacked("SolveSylvester")
+def solve_sylvester_stack(node, ins, raw, env):
+    """One batched Bartels-Stewart call above the Kronecker bound; below it, and with two operands, the items are looped"""
+    from pytensor_amd.dispatch.riccati import out_dtype
+
+    if len(ins) != 3 or sylvester_tier(ins[0].shape[-1], ins[1].shape[-1]) != "schur":
+        return None
+    return [solve_sylvester_schur(env, *ins, bool(node.params["core_params"].get("b_is_a_t", False)), out_dtype(env, node))]
+
+
 @handler("SolveSylvester")
 def solve_sylvester(node, inputs, env):
     """``A X + X B = C`` (linalg/solvers/linear_control.py:117 ``SolveSylvester``; the reference builds
@@ -759,7 +743,7 @@ def solve_sylvester(node, inputs, env):
     from pytensor_amd.dispatch.lu import solve_general
     from pytensor_amd.dispatch.riccati import out_dtype
 
-    A, B, Cm = _same_float(env, inputs, "SolveSylvester")
+    A, B, Cm = _lapack_operands(env, "SolveSylvester", *inputs)
     m, n = A.shape[0], B.shape[0]
     if A.shape != (m, m) or B.shape != (n, n) or Cm.shape != (m, n):
         raise ValueError(f"SolveSylvester: incompatible shapes {A.shape}, {B.shape}, {Cm.shape}")
@@ -780,5 +764,5 @@ def solve_sylvester(node, inputs, env):
                         Im.view(shape, (Im.strides[0], 0, Im.strides[1], 0)), B.view(shape, (0, B.strides[1], 0, B.strides[0]))],
              [dt] * 4, dt, shape)
     mn = m * n
-    x = solve_general(env, K.view((mn, mn), (mn, 1)), _reshape(Cm, (mn,)), 1)
+    x = solve_general(env, K.view((mn, mn), (mn, 1)), as_contiguous(Cm, (mn,)), 1)
     return [x.view((m, n), (n, 1))]

@@ -11,8 +11,10 @@ import numpy as np
 
 from pytensor_amd import ffi
 from pytensor_amd.device import DeviceArray, copy_into
-from pytensor_amd.dispatch import handler
+from pytensor_amd.dispatch import HANDLERS, STACKED, handler, stacked
+from pytensor_amd.dispatch.batch import batchify
 from pytensor_amd.executor import HostValue
+from pytensor_amd.ir import CoreNode
 
 
 def _dt(x):
@@ -47,34 +49,13 @@ def _lapack_operands(env, what, *vals):
     return [x if np.dtype(x.dtype) == work else _cast(env, x.contiguous(), work) for x in xs]
 
 
-def _batchify(x: DeviceArray, core_ndim: int, bshape):
-    """Broadcast leading dims to ``bshape`` and return a contiguous (batch, *core) array."""
-    core = x.shape[x.ndim - core_ndim :]
-    lead = x.shape[: x.ndim - core_ndim]
-    lead = (1,) * (len(bshape) - len(lead)) + lead
-    nb = int(np.prod(bshape)) if bshape else 1
-    if lead == tuple(bshape) and x.is_contiguous():
-        return x.view((nb, *core), _cs((nb, *core)))
-    out = DeviceArray.empty((*bshape, *core), x.dtype)
-    copy_into(out, x.view((*lead, *core), (0,) * (len(lead) - (x.ndim - core_ndim)) + x.strides))
-    return out.view((nb, *core), _cs((nb, *core)))
-
-
-def _cs(shape):
-    st, acc = [], 1
-    for s in reversed(shape):
-        st.append(acc)
-        acc *= max(int(s), 1)
-    return tuple(reversed(st))
-
-
 def cholesky_device(env, a: DeviceArray, lower: bool) -> DeviceArray:
     (a,) = _lapack_operands(env, "Cholesky", a)
     if a.shape[-1] != a.shape[-2]:
         raise ValueError("Cholesky: matrix must be square")
     n = a.shape[-1]
     bshape = a.shape[:-2]
-    ab = _batchify(a, 2, bshape)
+    ab = batchify(a, 2, bshape)
     out = DeviceArray.empty(a.shape, a.dtype)
     if out.size:
         ffi.check(env.lib.pthip_potrf(_dt(a), int(lower), ab.shape[0], n, ab.ptr, out.ptr))
@@ -104,9 +85,9 @@ def trsm_device(env, T: DeviceArray, b: DeviceArray, lower, unit, b_ndim, trans=
         bm = b.contiguous()
         sBb = 0
     else:
-        Tm = _batchify(T, 2, bshape)
+        Tm = batchify(T, 2, bshape)
         sTb, sT0, sT1 = Tm.strides
-        bm = _batchify(b, b_ndim, bshape)
+        bm = batchify(b, b_ndim, bshape)
         sBb = bm.strides[0]
     ffi.check(
         env.lib.pthip_trsm(_dt(T), int(lower), int(trans), int(unit), nb, n, nrhs, Tm.ptr, sTb, sT0, sT1, bm.ptr, sBb, out.ptr)
@@ -159,75 +140,38 @@ def cholesky_solve(node, inputs, env):
     return [cho_solve_device(env, c, b, node.params["lower"], node.params["b_ndim"])]
 
 
+@stacked("Cholesky")
+def cholesky_stack(node, ins, raw, env):
+    return [cholesky_device(env, ins[0], node.params["core_params"]["lower"])]
+
+
+@stacked("SolveTriangular")
+def solve_triangular_stack(node, ins, raw, env):
+    cp = node.params["core_params"]
+    return [trsm_device(env, ins[0], ins[1], cp["lower"], cp["unit_diagonal"], cp["b_ndim"])]
+
+
+@stacked("CholeskySolve")
+def cholesky_solve_stack(node, ins, raw, env):
+    cp = node.params["core_params"]
+    return [cho_solve_device(env, ins[0], ins[1], cp["lower"], cp["b_ndim"])]
+
+
 @handler("Blockwise")
 def blockwise(node, inputs, env):
-    p = node.params
-    cp = p["core_params"]
+    """The core op's ``STACKED`` entry takes the whole stack; without one, or where it answers None, the items are
+    looped.  Every operand is converted first, a host-known scalar included: the entry and the loop both get ``ins``."""
     ins = [env.to_device(i) for i in inputs]
-    if p["core_op"] == "Cholesky":
-        return [cholesky_device(env, ins[0], cp["lower"])]
-    if p["core_op"] == "SolveTriangular":
-        return [trsm_device(env, ins[0], ins[1], cp["lower"], cp["unit_diagonal"], cp["b_ndim"])]
-    if p["core_op"] == "CholeskySolve":
-        return [cho_solve_device(env, ins[0], ins[1], cp["lower"], cp["b_ndim"])]
-    if p["core_op"] in ("Solve", "Det", "SLogDet"):
-        from pytensor_amd.dispatch import lu
-
-        if p["core_op"] == "Solve":
-            return [lu._solve(env, cp, ins[0], ins[1])]
-        fake = type("_N", (), {"params": cp})
-        return (lu.det if p["core_op"] == "Det" else lu.slogdet)(fake, ins, env)
-    if p["core_op"] == "MatrixInverse":  # (one launch for the whole stack up to n = 64: lu.solve_tier)
-        from pytensor_amd.dispatch import lu
-
-        return lu.matrix_inverse(type("_N", (), {"params": cp}), ins, env)
-    if p["core_op"] == "LUFactor":
-        from pytensor_amd.dispatch import lu
-
-        return list(lu.lu_factor_device(env, ins[0]))
-    if p["core_op"] == "PivotToPermutations":
-        from pytensor_amd.dispatch import lu
-
-        return lu.pivot_to_permutations(type("_N", (), {"params": cp}), ins, env)
-    if p["core_op"] == "Eigh":  # (standard or generalised: every kernel either is composed of takes the batch)
-        from pytensor_amd.dispatch import lu
-
-        return lu.eigh(type("_N", (), {"params": cp}), ins, env)
-    if p["core_op"] == "QR":  # (geqrf / geqp3, orgqr and triu each take the whole stack in one launch)
-        from pytensor_amd.dispatch import decomp
-
-        return decomp.qr_op(type("_N", (), {"params": cp}), ins, env)
-    if p["core_op"] in ("SVD", "MatrixPinv"):  # (one launch up to max(m, n) = 64, batched kernels above: decomp.svd_tier)
-        from pytensor_amd.dispatch import decomp
-
-        return (decomp.svd_stack_op if p["core_op"] == "SVD" else decomp.pinv_stack_op)(type("_N", (), {"params": cp}), ins, env)
-    if p["core_op"] == "SolveDiscreteARE":  # (one launch for the whole batch up to m = 64)
-        from pytensor_amd.dispatch import riccati
-
-        return [riccati.dare_device(env, *ins, riccati.out_dtype(env, node))]
-    if p["core_op"] == "SolveSylvester" and len(ins) == 3:  # (above the Kronecker bound: one batched call)
-        from pytensor_amd.dispatch import decomp, riccati
-
-        if decomp.sylvester_tier(ins[0].shape[-1], ins[1].shape[-1]) == "schur":
-            return [decomp.solve_sylvester_schur(env, *ins, bool(cp.get("b_is_a_t", False)), riccati.out_dtype(env, node))]
-    if p["core_op"] in ("Convolve1d", "Convolve2d") and len(ins) == 3:  # (one launch for the whole stack: misc.conv_tier)
-        from pytensor_amd.dispatch import misc
-
-        outs = (misc.convolve1d_stack if p["core_op"] == "Convolve1d" else misc.convolve2d_stack)(node, inputs, env)
-        if outs is not None:
-            return outs
-    return _blockwise_loop(node, ins, env, inputs)
+    stack = STACKED.get(node.params["core_op"])
+    outs = stack(node, ins, inputs, env) if stack is not None else None
+    return outs if outs is not None else _blockwise_loop(node, ins, env, inputs)
 
 
-
-def _blockwise_loop(node, ins, env, raw=None):
+def _blockwise_loop(node, ins, env, raw):
     """Any other core op with a device handler: loop the broadcast batch on the host, one core
     call per item on views of the operands (``Blockwise.perform``, pytensor/tensor/blockwise.py:
     542: gufunc semantics).  What ``vectorize`` makes of small helper ops — the row gather
     ``b[perm]`` and the pivot bookkeeping of a batched ``lu_solve`` — not a hot path."""
-    from pytensor_amd.device import copy_into
-    from pytensor_amd.dispatch import HANDLERS
-
     p = node.params
     core = HANDLERS.get(p["core_op"])
     if p["core_op"] == "__inline__":
@@ -259,18 +203,17 @@ def _blockwise_loop(node, ins, env, raw=None):
         pad = len(bshape) - len(lead)
         strides = (0,) * pad + tuple(0 if (s == 1 and bshape[pad + d] != 1) else st for d, (s, st) in enumerate(zip(lead, a.strides[: len(lead)])))
         views.append((a, strides, a.shape[a.ndim - c :], a.strides[a.ndim - c :]))
-    fake = type("_Core", (), {"params": p["core_params"], "inputs": list(node.inputs), "outputs": list(node.outputs)})
+    item_node = CoreNode(p["core_params"], list(node.inputs), list(node.outputs))
     outs = None
     saved = env.donated
     env.donated = frozenset()
     try:
         for idx in np.ndindex(*bshape):
             item = [a.view(cs, cst, sum(i * st for i, st in zip(idx, bst))) for a, bst, cs, cst in views]
-            if raw is not None:
-                # an unbatched host-known operand (the step count of a vectorised Scan) stays on the host: the core
-                # handler reads it without a device round trip
-                item = [r if (isinstance(r, HostValue) and r.a.ndim == c) else it for it, r, c in zip(item, raw, core_ndims)]
-            rs = [env.to_device(r) for r in core(fake, item, env)]
+            # an unbatched host-known operand (the step count of a vectorised Scan) stays on the host: the core
+            # handler reads it without a device round trip
+            item = [r if (isinstance(r, HostValue) and r.a.ndim == c) else it for it, r, c in zip(item, raw, core_ndims)]
+            rs = [env.to_device(r) for r in core(item_node, item, env)]
             if outs is None:
                 outs = [DeviceArray.empty((*bshape, *r.shape), r.dtype) for r in rs]
             for o, r in zip(outs, rs):

@@ -12,21 +12,21 @@ from __future__ import annotations
 import numpy as np
 
 from pytensor_amd import ffi
-from pytensor_amd.device import DeviceArray, contiguous_strides
-from pytensor_amd.dispatch import handler
-from pytensor_amd.dispatch.linalg import _batchify, _dt, _require_float, cho_solve_device, cholesky_device, trsm_device
+from pytensor_amd.device import DeviceArray, contiguous_strides, copy_into
+from pytensor_amd.dispatch import handler, stacked
+from pytensor_amd.dispatch.batch import batch_strides, batchify, collapse_batch, walk_outer
+from pytensor_amd.dispatch.linalg import _dt, _lapack_operands, _require_float, cho_solve_device, cholesky_device, trsm_device
+from pytensor_amd.executor import HostValue
 
 
 def getrf_device(env, a: DeviceArray, flag_singular=False):
     """(LU, perm, sign, logabsdet) of a (..., n, n) array; batch dims flattened."""
-    from pytensor_amd.dispatch.linalg import _lapack_operands
-
     (a,) = _lapack_operands(env, "LU", a)
     n = a.shape[-1]
     if a.shape[-2] != n:
         raise ValueError("expected a square matrix")
     bshape = a.shape[:-2]
-    ab = _batchify(a, 2, bshape)
+    ab = batchify(a, 2, bshape)
     nb = ab.shape[0]
     LU = DeviceArray.empty((nb, n, n), a.dtype)
     perm = DeviceArray.empty((nb, n), "int64")
@@ -35,8 +35,6 @@ def getrf_device(env, a: DeviceArray, flag_singular=False):
     if nb and n:
         ffi.check(env.lib.pthip_getrf(_dt(a), nb, n, ab.ptr, LU.ptr, perm.ptr, sign.ptr, logabs.ptr, int(flag_singular)))
     elif nb:  # 0 x 0: det = 1
-        from pytensor_amd.executor import HostValue
-
         sign = env.to_device(HostValue(np.ones((nb,), dtype=a.dtype)))
         logabs = env.to_device(HostValue(np.zeros((nb,), dtype=a.dtype)))
     return LU, perm, sign, logabs, bshape
@@ -71,47 +69,22 @@ def solve_tier(n: int, nb: int) -> str:
     return "composed" if nb >= 2 else "loop"
 
 
-def _batch_strides(x: DeviceArray, core_ndim: int, bshape):
-    """Element strides of ``x``'s leading dims broadcast to ``bshape`` (0 along a broadcast dim)."""
-    lead = x.shape[: x.ndim - core_ndim]
-    pad = len(bshape) - len(lead)
-    return (0,) * pad + tuple(0 if s == 1 else st for s, st in zip(lead, x.strides[: len(lead)]))
-
-
-def _collapse_batch(bshape, *stride_sets):
-    """Fold the batch dims, innermost first, into one count with ONE stride per operand — what a kernel that takes
-    a batch stride can walk by itself.  Returns (outer, inner, strides): ``outer`` lists the (size, stride per
-    operand) of the leading dims that do not fold (the caller loops them), ``inner`` the folded count."""
-    dims = [(s, [ss[d] for ss in stride_sets]) for d, s in enumerate(bshape) if s != 1]
-    inner, st = 1, [0] * len(stride_sets)
-    while dims:
-        s, sts = dims[-1]
-        if inner > 1 and any(a != b * inner for a, b in zip(sts, st)):
-            break
-        if inner == 1:
-            st = list(sts)
-        inner *= s
-        dims.pop()
-    return dims, inner, st
-
-
 def _gesv_wave(env, A: DeviceArray, b, b_ndim: int, out: DeviceArray, bshape, flag_singular: bool):
     """``out`` (contiguous, (*bshape, *core)) = A^-1 b (``b`` None: the inverse) through pthip_gesv_batched.
     Broadcast and strided batch dims go to the kernel as strides; dims that do not fold into one stride (``A``
     (5,1,n,n) against ``b`` (1,7,n,k)) are walked here, one launch per outer index, and nothing is copied."""
     n = A.shape[-1]
     nrhs = n if b is None else (1 if b_ndim == 1 else b.shape[-1])
-    sets = [_batch_strides(A, 2, bshape)]
+    sets = [batch_strides(A, 2, bshape)]
     if b is not None:
         core_b = b.shape[b.ndim - b_ndim :]
         # (the stride of a core dim of length 1 is never read: it forces no copy)
         if any(s != 1 and st != c for s, st, c in zip(core_b, b.strides[b.ndim - b_ndim :], contiguous_strides(core_b))):
             b = b.contiguous()
-        sets.append(_batch_strides(b, b_ndim, bshape))
-    outer, inner, st = _collapse_batch(bshape, *sets)
+        sets.append(batch_strides(b, b_ndim, bshape))
+    outer, inner, st = collapse_batch(bshape, *sets)
     isz, per = A.itemsize, n * nrhs
-    for f, idx in enumerate(np.ndindex(*[s for s, _ in outer])):
-        offs = [sum(i * sts[k] for i, (_, sts) in zip(idx, outer)) for k in range(len(sets))]
+    for f, offs in walk_outer(outer, len(sets)):
         ffi.check(env.lib.pthip_gesv_batched(
             _dt(A), inner, n, nrhs, A.ptr + offs[0] * isz, st[0], A.strides[-2], A.strides[-1],
             None if b is None else b.ptr + offs[1] * isz, 0 if b is None else st[1], out.ptr + f * inner * per * isz,
@@ -125,7 +98,7 @@ def _solve_composed(env, A: DeviceArray, b, b_ndim: int, out: DeviceArray, bshap
     nb = int(np.prod(bshape))
     nrhs = n if b is None else (1 if b_ndim == 1 else b.shape[-1])
     shared = int(np.prod(A.shape[:-2])) == 1
-    LU, perm, _, _, _ = getrf_device(env, A.view((n, n), A.strides[-2:]) if shared else _batchify(A, 2, bshape).view((nb, n, n), (n * n, n, 1)),
+    LU, perm, _, _, _ = getrf_device(env, A.view((n, n), A.strides[-2:]) if shared else batchify(A, 2, bshape).view((nb, n, n), (n * n, n, 1)),
                                      flag_singular=flag_singular)
     sTb = 0 if shared else n * n
     bptr, sBb = None, 0
@@ -133,7 +106,7 @@ def _solve_composed(env, A: DeviceArray, b, b_ndim: int, out: DeviceArray, bshap
         if int(np.prod(b.shape[: b.ndim - b_ndim])) == 1:
             bm = b.contiguous()
         else:
-            bm, sBb = _batchify(b, b_ndim, bshape), n * nrhs
+            bm, sBb = batchify(b, b_ndim, bshape), n * nrhs
         bptr = bm.ptr
     pb = DeviceArray.empty((nb, n, nrhs), A.dtype)
     y = DeviceArray.empty((nb, n, nrhs), A.dtype)
@@ -169,16 +142,14 @@ def solve_general(env, A: DeviceArray, b: DeviceArray, b_ndim: int) -> DeviceArr
         y = trsm_device(env, lu, pb, True, True, b_ndim)
         return trsm_device(env, lu, y, False, False, b_ndim)
     # (at most one item behind leading dims of length 1 — or none at all)
-    Ab = _batchify(A, 2, bshape)
-    bbm = _batchify(b, b_ndim, bshape)
+    Ab = batchify(A, 2, bshape)
+    bbm = batchify(b, b_ndim, bshape)
     out = DeviceArray.empty((*bshape, *core_b), b.dtype)
     step = int(np.prod(core_b)) if core_b else 1
     for k in range(Ab.shape[0]):
         Ak = Ab.view((n, n), (n, 1), k * n * n)
         bk = bbm.view(core_b, contiguous_strides(core_b), k * step)
         xk = solve_general(env, Ak, bk, b_ndim)
-        from pytensor_amd.device import copy_into
-
         copy_into(out.view(core_b, contiguous_strides(core_b), k * step), xk)
     return out
 
@@ -202,15 +173,14 @@ def _gbsv(env, A: DeviceArray, b: DeviceArray, b_ndim: int, out: DeviceArray, bs
     core_b = b.shape[b.ndim - b_ndim :]
     if any(s != 1 and st != c for s, st, c in zip(core_b, b.strides[b.ndim - b_ndim :], contiguous_strides(core_b))):
         b = b.contiguous()
-    outer, inner, st = _collapse_batch(bshape, _batch_strides(A, 2, bshape), _batch_strides(b, b_ndim, bshape))
+    outer, inner, st = collapse_batch(bshape, batch_strides(A, 2, bshape), batch_strides(b, b_ndim, bshape))
     isz, per = A.itemsize, n * nrhs
     scanned = 1 if st[0] == 0 else inner
     band = DeviceArray.empty((scanned, 2), "int32")
     # a band that does not fit the LDS works in a dense slab per item: what the LU copy of the general path costs
     ws_bytes = int(env.lib.pthip_gbsv_workspace(_dt(A), inner, n))
     ws = DeviceArray.empty((ws_bytes,), "uint8") if ws_bytes else None
-    for f, idx in enumerate(np.ndindex(*[s for s, _ in outer])):
-        offs = [sum(i * sts[k] for i, (_, sts) in zip(idx, outer)) for k in range(2)]
+    for f, offs in walk_outer(outer, 2):
         ffi.check(env.lib.pthip_band_scan(_dt(A), scanned, n, A.ptr + offs[0] * isz, st[0], A.strides[-2], A.strides[-1], band.ptr))
         ffi.check(env.lib.pthip_gbsv_batched(
             _dt(A), inner, n, nrhs, A.ptr + offs[0] * isz, st[0], A.strides[-2], A.strides[-1], b.ptr + offs[1] * isz, st[1],
@@ -239,8 +209,6 @@ def solve_banded(env, A: DeviceArray, b: DeviceArray, b_ndim: int) -> DeviceArra
 
 
 def _solve(env, p, A, b):
-    from pytensor_amd.dispatch.linalg import _lapack_operands
-
     A, b = _lapack_operands(env, "Solve", A, b)  # (integer / float16 operands: LAPACK's working type)
     assume = p["assume_a"]
     if assume == "pos":
@@ -280,10 +248,13 @@ def lu_factor(node, inputs, env):
     return list(lu_factor_device(env, env.to_device(inputs[0])))
 
 
-@handler("PivotToPermutations")
-def pivot_to_permutations(node, inputs, env):
+@stacked("LUFactor")
+def lu_factor_stack(node, ins, raw, env):
+    return list(lu_factor_device(env, ins[0]))
+
+
+def pivots_to_perm_device(env, piv: DeviceArray, inverse: bool) -> DeviceArray:
     """lu.py:206-231: the permutation (or its inverse) LAPACK's sequential row interchanges amount to."""
-    piv = env.to_device(inputs[0])
     if piv.dtype.kind not in "iu" or piv.itemsize not in (4, 8):
         raise TypeError(f"PivotToPermutations: integer pivots expected, got {piv.dtype}")
     n = piv.shape[-1]
@@ -292,8 +263,18 @@ def pivot_to_permutations(node, inputs, env):
     nb = int(np.prod(bshape)) if bshape else 1
     out = DeviceArray.empty(piv.shape, "int64")
     if nb and n:
-        ffi.check(env.lib.pthip_pivots_to_perm(pc.itemsize, int(bool(node.params["inverse"])), nb, n, pc.ptr, out.ptr))
-    return [out]
+        ffi.check(env.lib.pthip_pivots_to_perm(pc.itemsize, int(bool(inverse)), nb, n, pc.ptr, out.ptr))
+    return out
+
+
+@handler("PivotToPermutations")
+def pivot_to_permutations(node, inputs, env):
+    return [pivots_to_perm_device(env, env.to_device(inputs[0]), node.params["inverse"])]
+
+
+@stacked("PivotToPermutations")
+def pivot_to_permutations_stack(node, ins, raw, env):
+    return [pivots_to_perm_device(env, ins[0], node.params["core_params"]["inverse"])]
 
 
 @handler("Solve")
@@ -302,16 +283,15 @@ def solve(node, inputs, env):
     return [_solve(env, node.params, A, b)]
 
 
-def _det(env, x):
-    LU, perm, sign, logabs, bshape = getrf_device(env, x)
-    return sign, logabs, bshape
+@stacked("Solve")
+def solve_stack(node, ins, raw, env):
+    return [_solve(env, node.params["core_params"], ins[0], ins[1])]
 
 
-@handler("Det")
-def det(node, inputs, env):
+def det_device(env, x: DeviceArray) -> DeviceArray:
     from pytensor_amd.dispatch.elemwise import launch_elemwise
 
-    sign, logabs, bshape = _det(env, env.to_device(inputs[0]))
+    _, _, sign, logabs, bshape = getrf_device(env, x)
     dt = str(sign.dtype)
     # det = sign * exp(log|det|): how np.linalg.det finishes too (umath_linalg det_from_slogdet)
     body = {
@@ -320,20 +300,37 @@ def det(node, inputs, env):
         "outs": [["t", 1]],
     }
     outs, _, _ = launch_elemwise(body, [sign, logabs], sign.shape, [dt], None, env)
-    return [outs[0].view(bshape, contiguous_strides(bshape))]
+    return outs[0].view(bshape, contiguous_strides(bshape))
+
+
+@handler("Det")
+def det(node, inputs, env):
+    return [det_device(env, env.to_device(inputs[0]))]
+
+
+@stacked("Det")
+def det_stack(node, ins, raw, env):
+    return [det_device(env, ins[0])]
+
+
+def slogdet_device(env, x: DeviceArray):
+    _, _, sign, logabs, bshape = getrf_device(env, x)
+    return [sign.view(bshape, contiguous_strides(bshape)), logabs.view(bshape, contiguous_strides(bshape))]
 
 
 @handler("SLogDet")
 def slogdet(node, inputs, env):
-    sign, logabs, bshape = _det(env, env.to_device(inputs[0]))
-    return [sign.view(bshape, contiguous_strides(bshape)), logabs.view(bshape, contiguous_strides(bshape))]
+    return slogdet_device(env, env.to_device(inputs[0]))
 
 
-@handler("MatrixInverse")
-def matrix_inverse(node, inputs, env):
+@stacked("SLogDet")
+def slogdet_stack(node, ins, raw, env):
+    return slogdet_device(env, ins[0])
+
+
+def matrix_inverse_device(env, x: DeviceArray) -> DeviceArray:
     """``np.linalg.inv`` of a (..., n, n) stack (LinAlgError when an item is singular), by the tiers of
     ``solve_tier`` with the identity as the right-hand side (generated on the device)."""
-    x = env.to_device(inputs[0])
     n = x.shape[-1]
     if x.ndim < 2 or x.shape[-2] != n:
         raise ValueError("MatrixInverse: expected square matrices")
@@ -344,71 +341,83 @@ def matrix_inverse(node, inputs, env):
         out = DeviceArray.empty(x.shape, x.dtype)
         if out.size:
             (_gesv_wave if tier == "wave" else _solve_composed)(env, x, None, 2, out, bshape, True)
-        return [out]
+        return out
     if nb == 0:
-        return [DeviceArray.empty(x.shape, x.dtype)]
+        return DeviceArray.empty(x.shape, x.dtype)
     LU, perm, _, _, _ = getrf_device(env, x.view((n, n), x.strides[-2:]), flag_singular=True)  # np.linalg.inv raises when singular
     lu = LU.view((n, n), (n, 1))
     pb = DeviceArray.empty((n, n), x.dtype)  # P * I, built on the device (no upload per call)
     ffi.check(env.lib.pthip_permuted_identity(_dt(x), n, perm.ptr, pb.ptr))
     y = trsm_device(env, lu, pb, True, True, 2)
-    return [trsm_device(env, lu, y, False, False, 2).view(x.shape, contiguous_strides(x.shape))]
+    return trsm_device(env, lu, y, False, False, 2).view(x.shape, contiguous_strides(x.shape))
 
 
-@handler("Eigh")
-def eigh(node, inputs, env):
+@handler("MatrixInverse")
+def matrix_inverse(node, inputs, env):
+    return [matrix_inverse_device(env, env.to_device(inputs[0]))]
+
+
+@stacked("MatrixInverse")
+def matrix_inverse_stack(node, ins, raw, env):
+    return [matrix_inverse_device(env, ins[0])]
+
+
+def eigh_device(env, inputs, lower: bool):
     """``Eigh`` of the standard problem (linalg/decomposition/eigen.py:102; perform 177-195):
-    eigenvalues ascending, eigenvectors as columns, the chosen triangle only (csrc/eigh.hip).
-    Leading dims are a batch (``Blockwise``)."""
+    eigenvalues ascending, eigenvectors as columns, the chosen triangle only (csrc/eigh.hip); with two operands the
+    generalised problem.  Leading dims are a batch (``Blockwise``)."""
     if len(inputs) == 2:
-        return _eigh_generalised(node, inputs, env)
-    from pytensor_amd.dispatch.linalg import _lapack_operands
-
+        return _eigh_generalised(env, inputs, lower)
     (a,) = _lapack_operands(env, "Eigh", inputs[0])
     n = a.shape[-1]
     if a.shape[-2] != n:
         raise ValueError("Eigh: expected a square matrix")
     bshape = a.shape[:-2]
-    ab = _batchify(a, 2, bshape)
+    ab = batchify(a, 2, bshape)
     nb = ab.shape[0]
     w = DeviceArray.empty((nb, n), a.dtype)
     v = DeviceArray.empty((nb, n, n), a.dtype)
     if nb and n:
-        ffi.check(env.lib.pthip_eigh(_dt(a), nb, n, int(node.params["lower"]), ab.ptr, w.ptr, v.ptr))
+        ffi.check(env.lib.pthip_eigh(_dt(a), nb, n, int(lower), ab.ptr, w.ptr, v.ptr))
     return [w.view((*bshape, n), contiguous_strides((*bshape, n))), v.view((*bshape, n, n), contiguous_strides((*bshape, n, n)))]
 
+
+@handler("Eigh")
+def eigh(node, inputs, env):
+    return eigh_device(env, inputs, node.params["lower"])
+
+
+@stacked("Eigh")
+def eigh_stack(node, ins, raw, env):
+    return eigh_device(env, ins, node.params["core_params"]["lower"])
 
 
 def _symmetrize(env, x: DeviceArray, lower: bool) -> DeviceArray:
     n = x.shape[-1]
     bshape = x.shape[:-2]
-    xb = _batchify(x, 2, bshape)
+    xb = batchify(x, 2, bshape)
     out = DeviceArray.empty(xb.shape, x.dtype)
     if out.size:
         ffi.check(env.lib.pthip_symmetrize(_dt(x), xb.shape[0], n, int(lower), xb.ptr, out.ptr))
     return out.view((*bshape, n, n), contiguous_strides((*bshape, n, n)))
 
 
-def _eigh_generalised(node, inputs, env):
+def _eigh_generalised(env, inputs, lower):
     """``A v = w B v`` (Eigh with two inputs; perform = ``scipy.linalg.eigh(a, b, lower=)``, LAPACK
     sygvd): the same reduction LAPACK's ``sygst`` does, out of kernels that exist — ``B = L L^T``
     (potrf), ``C = L^-1 A L^-T`` (two multi-rhs triangular solves), the standard problem for C
     (Jacobi), ``v = L^-T y``.  Eigenvectors come out B-orthonormal (``v^T B v = I``) like scipy's.  Every one of
     those kernels takes a batch, so leading dims are a batch here too (``Blockwise``)."""
-    from pytensor_amd.dispatch.linalg import _lapack_operands
-
     a, b = _lapack_operands(env, "Eigh", *inputs)
     n = a.shape[-1]
     if a.shape[-2] != n or b.shape[-2:] != (n, n):
         raise ValueError(f"Eigh: incompatible shapes {a.shape} and {b.shape}")
-    lower = bool(node.params["lower"])
     A = _symmetrize(env, a, lower)
     B = _symmetrize(env, b, lower)
     L = cholesky_device(env, B, True)
     Y = trsm_device(env, L, A, True, False, 2)  # L Y = A  (leading dims: a batch, broadcast by the solve)
     Yt = Y.view(Y.shape, (*Y.strides[:-2], Y.strides[-1], Y.strides[-2])).contiguous()
     Cm = trsm_device(env, L, Yt, True, False, 2)  # L C = Y^T  ->  C = L^-1 A L^-T (symmetric)
-    fake = type("_N", (), {"params": {"lower": True}})
-    w, y = eigh(fake, [Cm], env)
+    w, y = eigh_device(env, [Cm], True)
     v = trsm_device(env, L, y, True, False, 2, trans=True)  # L^T v = y
     return [w, v]

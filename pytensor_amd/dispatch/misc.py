@@ -16,17 +16,9 @@ import numpy as np
 
 from pytensor_amd import ffi
 from pytensor_amd.device import DeviceArray, contiguous_strides, copy_into
-from pytensor_amd.dispatch import handler
+from pytensor_amd.dispatch import handler, stacked
+from pytensor_amd.dispatch.batch import as_contiguous, batch_strides, batchify, merge_batch
 from pytensor_amd.executor import HostValue
-
-
-def _cs(shape):
-    return contiguous_strides(tuple(shape))
-
-
-def _reshaped(x: DeviceArray, shape) -> DeviceArray:
-    x = x.contiguous()
-    return x.view(tuple(shape), _cs(shape))
 
 
 def _ew(env, body_ops, ins, in_dtypes, out_dtype, shape):
@@ -66,7 +58,7 @@ def join_dims(node, inputs, env):
     x = env.to_device(inputs[0])
     a, n = int(node.params["start_axis"]), int(node.params["n_axes"])
     merged = int(np.prod(x.shape[a : a + n], dtype=np.int64)) if n else 1
-    return [_reshaped(x, (*x.shape[:a], merged, *x.shape[a + n :]))]
+    return [as_contiguous(x, (*x.shape[:a], merged, *x.shape[a + n :]))]
 
 
 @handler("SplitDims")
@@ -76,7 +68,7 @@ def split_dims(node, inputs, env):
     shape = _host_ints(env, inputs[1])
     if int(np.prod(shape, dtype=np.int64)) != x.shape[axis]:
         raise ValueError(f"cannot reshape array of size {x.size} into shape {(*x.shape[:axis], *shape, *x.shape[axis + 1:])}")
-    return [_reshaped(x, (*x.shape[:axis], *shape, *x.shape[axis + 1 :]))]
+    return [as_contiguous(x, (*x.shape[:axis], *shape, *x.shape[axis + 1 :]))]
 
 
 def _fill_line(env, out: DeviceArray, start: int, step: int, count: int, val):
@@ -103,7 +95,7 @@ def fill_diagonal(node, inputs, env):
     else:
         if len(set(a.shape)) != 1:
             raise ValueError("All dimensions of input must be of equal length")
-        _fill_line(env, a, 0, sum(_cs(a.shape)), a.shape[0], inputs[1])
+        _fill_line(env, a, 0, sum(contiguous_strides(a.shape)), a.shape[0], inputs[1])
     return [a]
 
 
@@ -354,7 +346,7 @@ def _unique_axis(node, inputs, env):
     want = [p["return_index"], p["return_inverse"], p["return_counts"]]
 
     def back(rows: DeviceArray, k: int) -> DeviceArray:
-        full = rows.view((k, *rest), _cs((k, *rest)))
+        full = rows.view((k, *rest), contiguous_strides((k, *rest)))
         inv = [order_ax.index(d) for d in range(x.ndim)]
         return full.view([full.shape[d] for d in inv], [full.strides[d] for d in inv]).contiguous()
 
@@ -532,29 +524,15 @@ def conv_tier(batch_shape, mode_shape=()):
     return "stack"
 
 
-def _merge_batch(bshape, *stride_sets):
-    """The batch as the fewest (size, strides per operand) dimensions a kernel can walk: length-1 dimensions dropped,
-    neighbours merged where every operand's strides allow it."""
-    dims = []
-    for d, n in enumerate(bshape):
-        if n == 1:
-            continue
-        st = [ss[d] for ss in stride_sets]
-        if dims and all(p == q * n for p, q in zip(dims[-1][1], st)):
-            dims[-1] = (dims[-1][0] * n, st)
-        else:
-            dims.append((n, st))
-    return dims
-
-
 def _conv_stack_operands(env, what, inputs, core_ndim):
     """(a, b, full, working dtype, result dtype, batch shape, the kernels' batch arguments) of a stacked convolution, or
     None where the node stays on the per-item loop.  Promotion is that of the unbatched handlers; a host-known ``full_mode`` is read on the host,
     a device scalar once."""
     from pytensor_amd.device import _i64arr
     from pytensor_amd.dispatch.elemwise import _cast
-    from pytensor_amd.dispatch.lu import _batch_strides
 
+    if len(inputs) != 3:
+        return None
     mode = inputs[2]
     a, b = (env.to_device(i) for i in inputs[:2])
     if a.ndim < core_ndim or b.ndim < core_ndim:
@@ -569,22 +547,22 @@ def _conv_stack_operands(env, what, inputs, core_ndim):
     ints = "iub" if core_ndim == 1 else "iu"
     kdt = dt if dt.name in ("float64", "float32", "int64") else np.dtype("int64" if dt.kind in ints else "float64")
     a, b = (t if np.dtype(t.dtype) == kdt else _cast(env, t.contiguous(), kdt) for t in (a, b))
-    sets = [_batch_strides(a, core_ndim, bshape), _batch_strides(b, core_ndim, bshape)]
-    dims = _merge_batch(bshape, *sets)
+    sets = [batch_strides(a, core_ndim, bshape), batch_strides(b, core_ndim, bshape)]
+    dims = merge_batch(bshape, *sets)
     if len(dims) > CONV_BATCH_DIMS:
-        from pytensor_amd.dispatch.linalg import _batchify
-
-        a, b = _batchify(a, core_ndim, bshape), _batchify(b, core_ndim, bshape)
+        a, b = batchify(a, core_ndim, bshape), batchify(b, core_ndim, bshape)
         dims = [(a.shape[0], [a.strides[0], b.strides[0]])]
     batch = (len(dims), _i64arr([n for n, _ in dims]), _i64arr([st[0] for _, st in dims]), _i64arr([st[1] for _, st in dims]))
     return a, b, full, kdt, dt, bshape, batch
 
 
-def convolve1d_stack(node, inputs, env):
-    """``Blockwise(Convolve1d)``: np.convolve of every pair of the broadcast stack, one launch; None: not taken"""
+@stacked("Convolve1d")
+def convolve1d_stack(node, ins, raw, env):
+    """``Blockwise(Convolve1d)``: np.convolve of every pair of the broadcast stack, one launch; None: not taken.  Reads
+    ``raw``: a host-known ``full_mode`` costs no device read."""
     from pytensor_amd.dispatch.elemwise import _cast
 
-    ops = _conv_stack_operands(env, "Convolve1d", inputs, 1)
+    ops = _conv_stack_operands(env, "Convolve1d", raw, 1)
     if ops is None:
         return None
     a, b, full, kdt, dt, bshape, batch = ops
@@ -597,12 +575,13 @@ def convolve1d_stack(node, inputs, env):
     return [out if kdt == dt else _cast(env, out, dt)]
 
 
-def convolve2d_stack(node, inputs, env):
+@stacked("Convolve2d")
+def convolve2d_stack(node, ins, raw, env):
     """``Blockwise(Convolve2d)``: scipy.signal.convolve (direct sums) of every pair of the broadcast stack, one launch;
     None: not taken"""
     from pytensor_amd.dispatch.elemwise import _cast
 
-    ops = _conv_stack_operands(env, "Convolve2d", inputs, 2)
+    ops = _conv_stack_operands(env, "Convolve2d", raw, 2)
     if ops is None:
         return None
     a, b, full, kdt, dt, bshape, batch = ops

@@ -189,9 +189,9 @@ def random_variable(node, inputs, env):
 
                 M, d, _ = svd_device(env, cov, True, True)
             else:
-                from pytensor_amd.dispatch.lu import eigh as eigh_handler
+                from pytensor_amd.dispatch.lu import eigh_device
 
-                d, M = eigh_handler(type("_N", (), {"params": {"lower": True}}), [cov], env)
+                d, M = eigh_device(env, [cov], True)
             dt = str(fdt)
             body = {"in_dtypes": [dt, dt], "out_dtypes": [dt],
                     "body": [{"op": "Sqrt", "in": [["i", 1]], "dtype": dt}, {"op": "Mul", "in": [["i", 0], ["t", 0]], "dtype": dt}], "outs": [["t", 1]]}

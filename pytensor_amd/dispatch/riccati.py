@@ -21,8 +21,9 @@ import numpy as np
 
 from pytensor_amd import ffi
 from pytensor_amd.device import DeviceArray, contiguous_strides, copy_into
-from pytensor_amd.dispatch import handler
-from pytensor_amd.dispatch.linalg import _batchify, _lapack_operands
+from pytensor_amd.dispatch import handler, stacked
+from pytensor_amd.dispatch.batch import batchify
+from pytensor_amd.dispatch.linalg import _lapack_operands
 
 MAX_SINGLE_LAUNCH = 64  # m of the one-kernel tier (csrc/riccati.hip DARE_MAX_M)
 MAX_DARE = 1024  # m of the composed tier
@@ -52,7 +53,7 @@ def dare_device(env, A, B, Q, R, out_dtype=None, with_steps=False):
         return (out, None) if with_steps else out
     if m > MAX_DARE:
         raise NotImplementedError(f"hip linker: SolveDiscreteARE with m = {m} (device tiers up to m = {MAX_DARE})")
-    Ab, Bb, Qb, Rb = (_batchify(x, 2, bshape) for x in (A, B, Q, R))
+    Ab, Bb, Qb, Rb = (batchify(x, 2, bshape) for x in (A, B, Q, R))
     ob = out.view((nb, m, m), contiguous_strides((nb, m, m)))
     steps = None
     if m <= MAX_SINGLE_LAUNCH and n <= m:
@@ -123,6 +124,11 @@ def solve_discrete_are(node, inputs, env):
         if x.ndim != 2:
             raise ValueError(f"SolveDiscreteARE: {what} must be a matrix, got {x.ndim} dimensions")
     return [dare_device(env, A, B, Q, R, out_dtype(env, node))]
+
+
+@stacked("SolveDiscreteARE")
+def solve_discrete_are_stack(node, ins, raw, env):
+    return [dare_device(env, *ins, out_dtype(env, node))]
 
 
 def out_dtype(env, node):

@@ -47,6 +47,16 @@ class Node:
 
 
 @dataclass
+class CoreNode:
+    """What a handler sees of a ``Blockwise`` node when the batch is looped item by item: the core op's params, the
+    Blockwise node's own inputs and outputs (dispatch/linalg.py::_blockwise_loop)."""
+
+    params: dict
+    inputs: list
+    outputs: list
+
+
+@dataclass
 class Graph:
     vars: dict = field(default_factory=dict)
     nodes: list = field(default_factory=list)

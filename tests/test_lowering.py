@@ -215,6 +215,23 @@ def test_op_coverage_of_the_registry(pt):
     assert missing == not_lowered, (sorted(missing - not_lowered), sorted(not_lowered - missing))
 
 
+def test_every_stacked_core_op_is_in_the_table(pt):
+    """``dispatch.STACKED`` holds every core op ``Blockwise`` has handed a whole stack so far, each registered from
+    the module that owns the op."""
+    from pytensor_amd.dispatch import STACKED
+
+    owners = {
+        "linalg": ("Cholesky", "SolveTriangular", "CholeskySolve"),
+        "lu": ("Solve", "Det", "SLogDet", "MatrixInverse", "LUFactor", "PivotToPermutations", "Eigh"),
+        "decomp": ("QR", "SVD", "MatrixPinv", "SolveSylvester"),
+        "riccati": ("SolveDiscreteARE",),
+        "misc": ("Convolve1d", "Convolve2d"),
+    }
+    for m, ops in owners.items():
+        for op in ops:
+            assert op in STACKED and STACKED[op].__module__ == f"pytensor_amd.dispatch.{m}", op
+
+
 def test_all_reduce_op_lowers_and_differentiates(pt):
     """The explicit collective (north_star: "the rare explicit all-reduce Op"): an ordinary Op for
     every linker (perform = the host reduction, identity on one rank), an ``AllReduce`` IR node

@@ -25,19 +25,19 @@ def test_solve_tier_boundaries():
 
 
 def test_batch_dims_fold_into_one_stride_per_operand():
-    from pytensor_amd.dispatch.lu import _collapse_batch
+    from pytensor_amd.dispatch.batch import collapse_batch
 
     n2 = 16
     # a contiguous stack against a contiguous stack: one launch
-    assert _collapse_batch((5, 7), (7 * n2, n2), (7 * 4, 4)) == ([], 35, [n2, 4])
+    assert collapse_batch((5, 7), (7 * n2, n2), (7 * 4, 4)) == ([], 35, [n2, 4])
     # A (n, n) against b (65, n): the matrix is shared (stride 0)
-    assert _collapse_batch((65,), (0,), (4,)) == ([], 65, [0, 4])
+    assert collapse_batch((65,), (0,), (4,)) == ([], 65, [0, 4])
     # A (5, 1, n, n) against b (1, 7, n, 3): the 7 fold (A shared), the 5 are walked
-    outer, inner, st = _collapse_batch((5, 7), (n2, 0), (0, 12))
+    outer, inner, st = collapse_batch((5, 7), (n2, 0), (0, 12))
     assert (inner, st) == (7, [0, 12]) and outer == [(5, [n2, 0])]
     # every second matrix of a larger stack; no batch at all
-    assert _collapse_batch((4,), (2 * n2,), (4,)) == ([], 4, [2 * n2, 4])
-    assert _collapse_batch((), (), ()) == ([], 1, [0, 0])
+    assert collapse_batch((4,), (2 * n2,), (4,)) == ([], 4, [2 * n2, 4])
+    assert collapse_batch((), (), ()) == ([], 1, [0, 0])
 
 
 def test_abi_declares_the_batched_solve_entry_points():
