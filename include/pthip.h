@@ -246,6 +246,18 @@ int64_t pthip_gemm_nslabs(int64_t batch, int64_t M, int64_t N, int64_t K);
 int pthip_gemm_partials(int dtype, int64_t batch, int64_t M, int64_t N, int64_t K, const void* A,
                         int64_t sAb, int64_t sA0, int64_t sA1, const void* B, int64_t sBb,
                         int64_t sB0, int64_t sB1, void* part, int64_t nslabs);
+/* float16 products (Dot / matmul / BatchedDot of halves: np.dot accumulates in a float and rounds once):
+ * out[b] (M×N, contiguous, float16) = half(A[b] (M×K) @ B[b] (K×N)), fp32 accumulation on
+ * v_mfma_f32_32x32x16_f16, ONE rounding to half (nearest even, overflow to ±inf).  Element strides; each
+ * operand needs one unit stride; batch stride 0 = shared.  K == 0 gives zeros.  One launch. */
+int pthip_hgemm(int64_t batch, int64_t M, int64_t N, int64_t K, const void* A, int64_t sAb,
+                int64_t sA0, int64_t sA1, const void* B, int64_t sBb, int64_t sB0, int64_t sB1,
+                void* out);
+/* out[i] (float16) = half(sum_j A[i*sA0 + j*sA1] * x[j*sx]), fp32 accumulation in a fixed order, one
+ * rounding; row layout (sA1 == 1), column layout (sA0 == 1) or any other strides; M == 1 is the
+ * inner product of two vectors.  One launch. */
+int pthip_hgemv(int64_t M, int64_t K, const void* A, int64_t sA0, int64_t sA1, const void* x,
+                int64_t sx, void* out);
 /* Loop-constant right operand of a skinny product (the recurrent weights of a Scan step:
  * Dot22/Gemm, blas/gemm.py:76,248, whose left operand has a few hundred rows at most), repacked
  * once per evaluation into the MFMA operand order the generated product+epilogue kernels stream:

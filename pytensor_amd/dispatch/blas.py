@@ -125,6 +125,11 @@ def gemv(node, inputs, env):
     ah, bh = _host_scalar(alpha), _host_scalar(beta)
     A, x = env.to_device(A), env.to_device(x)
     y = env.to_device(y)
+    if _is_half(A):  # the half product, then beta*y + alpha*t rounded per op as the reference's float16 arithmetic is
+        t = hgemv_device(env, A, x)
+        if y.shape[0] != A.shape[0]:
+            raise ValueError(f"Shape mismatch: y.shape[0] != A.shape[0] ({y.shape}, {A.shape})")
+        return [t if (ah, bh) == (1.0, 0.0) else _axpby(env, alpha, t, beta, y)]
     if ah is None or bh is None:  # alpha/beta computed on the device
         if y.shape[0] != A.shape[0]:
             raise ValueError(f"Shape mismatch: y.shape[0] != A.shape[0] ({y.shape}, {A.shape})")
@@ -196,6 +201,54 @@ def gemm_device(env, alpha, A, B, beta=0.0, Cm=None, batch=None):
     return out
 
 
+def _is_half(x) -> bool:
+    return str(x.dtype) == "float16"
+
+
+def hgemm_device(env, A, B, batch=None):
+    """out = half(A @ B) for float16 operands: fp32 accumulation on the matrix cores, one rounding (csrc/hgemm.hip);
+    A (.., M, K), B (.., K, N), a batch stride of 0 shares an operand.  One launch, nothing but the output allocated."""
+    if batch is None:
+        M, K = A.shape
+        K2, N = B.shape
+        nb = 1
+        sAb = sBb = 0
+        sA, sB = A.strides, B.strides
+    else:
+        nb, M, K = A.shape
+        nb2, K2, N = B.shape
+        if nb != nb2:
+            raise TypeError(f"Inputs [{A.shape}, {B.shape}] must have the same size in axis 0")
+        sAb, sBb = A.strides[0], B.strides[0]
+        sA, sB = A.strides[1:], B.strides[1:]
+    if K != K2:
+        raise ValueError(f"Shape mismatch: x has {K} cols but y has {K2} rows")
+    out = DeviceArray.empty((M, N) if batch is None else (nb, M, N), "float16")
+    if out.size == 0:
+        return out
+    env.timed(
+        f"hgemm_b{nb}_{M}x{N}x{K}",
+        lambda: ffi.check(env.lib.pthip_hgemm(nb, M, N, K, A.ptr, sAb, sA[0], sA[1], B.ptr, sBb, sB[0], sB[1], out.ptr)),
+    )
+    return out
+
+
+def hgemv_device(env, A, x):
+    """out = half(A @ x) for a float16 (M, K) view ``A`` of any strides and a (K,) vector: fp32 accumulation in a fixed
+    order, one rounding (csrc/hgemm.hip); bandwidth-bound, never a GEMM with N = 1."""
+    M, K = A.shape
+    if x.shape[0] != K:
+        raise ValueError(f"Shape mismatch: A.shape[1] != x.shape[0] ({A.shape}, {x.shape})")
+    out = DeviceArray.empty((M,), "float16")
+    if M:
+        sA0, sA1 = A.strides
+        env.timed(
+            f"hgemv_{M}x{K}_{'col' if sA0 == 1 and sA1 != 1 and M > 1 else 'row'}",
+            lambda: ffi.check(env.lib.pthip_hgemv(M, K, A.ptr, sA0, sA1, x.ptr, x.strides[0], out.ptr)),
+        )
+    return out
+
+
 def _prep2d(x):
     return _unit_stride_2d(x)
 
@@ -203,6 +256,8 @@ def _prep2d(x):
 @handler("Dot22")
 def dot22(node, inputs, env):
     x, y = (env.to_device(i) for i in inputs)
+    if _is_half(x):
+        return [hgemm_device(env, _prep2d(x), _prep2d(y))]
     return [gemm_device(env, 1.0, _prep2d(x), _prep2d(y))]
 
 
@@ -211,6 +266,8 @@ def dot22scalar(node, inputs, env):
     x, y, a = inputs
     x, y = env.to_device(x), env.to_device(y)
     ah = _host_scalar(a)
+    if _is_half(x):  # scalar * half(x @ y): two roundings, as Dot22Scalar.perform on halves
+        return [_axpby(env, a, hgemm_device(env, _prep2d(x), _prep2d(y)), 0.0, None)]
     if ah is None:
         return [_axpby(env, a, gemm_device(env, 1.0, _prep2d(x), _prep2d(y)), 0.0, None)]
     return [gemm_device(env, ah, _prep2d(x), _prep2d(y))]
@@ -221,6 +278,8 @@ def gemm(node, inputs, env):
     z, a, x, y, b = inputs
     z, x, y = env.to_device(z), env.to_device(x), env.to_device(y)
     ah, bh = _host_scalar(a), _host_scalar(b)
+    if _is_half(x):
+        return [_axpby(env, a, hgemm_device(env, _prep2d(x), _prep2d(y)), b, z)]
     if ah is None or bh is None:
         return [_axpby(env, a, gemm_device(env, 1.0, _prep2d(x), _prep2d(y)), b, z)]
     return [gemm_device(env, ah, _prep2d(x), _prep2d(y), bh, z)]
@@ -234,6 +293,11 @@ def _prep3d(x):
 @handler("BatchedDot")
 def batched_dot(node, inputs, env):
     x, y = (env.to_device(i) for i in inputs)
+    if str(env.graph.vars[node.outputs[0]].dtype) == "float16":
+        from pytensor_amd.dispatch.elemwise import _cast
+
+        x, y = (v if str(v.dtype) == "float16" else _cast(env, v, "float16") for v in (x, y))
+        return [hgemm_device(env, _prep3d(x), _prep3d(y), batch=True)]
     return [gemm_device(env, 1.0, _prep3d(x), _prep3d(y), batch=True)]
 
 
@@ -264,6 +328,22 @@ def _int_dot(env, x, y, out_dtype):
     return out
 
 
+def _half_dot(env, x, y):
+    """float16 ``Dot`` of every rank combination: matrix x matrix on the half MFMA tiles, the three forms with a
+    vector on the streaming matrix-vector kernel (the inner product is its M = 1)."""
+    if x.ndim > 2 or y.ndim > 2:
+        raise NotImplementedError("Dot with ndim > 2")
+    if x.ndim == 2 and y.ndim == 2:
+        return hgemm_device(env, _prep2d(x), _prep2d(y))
+    if x.ndim == 2:
+        return hgemv_device(env, x, y)
+    if y.ndim == 2:
+        return hgemv_device(env, y.view((y.shape[1], y.shape[0]), (y.strides[1], y.strides[0])), x)
+    if x.shape != y.shape:
+        raise ValueError(f"shapes {x.shape} and {y.shape} not aligned")
+    return hgemv_device(env, x.view((1, x.shape[0]), (0, x.strides[0])), y).view((), ())
+
+
 @handler("Dot")
 def dot(node, inputs, env):
     x, y = (env.to_device(i) for i in inputs)
@@ -276,6 +356,8 @@ def dot(node, inputs, env):
 
     x = x if str(x.dtype) == out_dtype else _cast(env, x, out_dtype)
     y = y if str(y.dtype) == out_dtype else _cast(env, y, out_dtype)
+    if out_dtype == "float16":
+        return [_half_dot(env, x, y)]
     if x.ndim == 2 and y.ndim == 2:
         return [gemm_device(env, 1.0, _prep2d(x), _prep2d(y))]
     if x.ndim == 2 and y.ndim == 1:
@@ -323,6 +405,8 @@ def seq_dot22(node, inputs, env):
     chunk = max(1, -(-int(os.environ.get("PTHIP_SCAN_CHUNK_ROWS", "4096")) // max(B, 1)))
     lazy_ok = (node.params.get("lazy") and os.environ.get("PTHIP_SCAN_OVERLAP", "0") == "1" and env.scheduler is None
                and T >= 3 * chunk and B * N > 0 and K > 0 and (N + 127) // 128 * ((chunk * B + 127) // 128) >= 128)
+    if _is_half(flat):
+        return [hgemm_device(env, flat, W2).view((T, B, N), (B * N, N, 1))]
     if not lazy_ok:
         out = gemm_device(env, 1.0, flat, W2)
         return [out.view((T, B, N), (B * N, N, 1))]

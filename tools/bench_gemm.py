@@ -1,6 +1,7 @@
 """Device time of pthip_gemm for a few shapes (HIP events around back-to-back launches).
 
-usage: python tools/bench_gemm.py
+usage: python tools/bench_gemm.py [shape indices]
+       python tools/bench_gemm.py half     (pthip_hgemm against cast + fp32 product + cast, four orientations)
 """
 import ctypes as C
 import json
@@ -32,9 +33,55 @@ def timed(lib, fn, reps):
     return ms.value / reps
 
 
+HALF_SHAPES = [(1, 4096, 4096, 4096), (512, 256, 256, 256), (1, 64, 4096, 4096)]
+ORIENT = (("NN", False, False), ("NT", False, True), ("TN", True, False), ("TT", True, True))
+
+
+def half_rows(lib):
+    """float16 products (pthip_hgemm) in the four operand orientations, next to what a user had to write before it
+    existed: cast both operands to float32, the fp32 product, cast back — same buffers, same run, alternating.  The
+    fp16 MFMA peak is 256 CUs x 4 SIMDs x 1024 flop/cycle (a 32x32x16 MFMA is 32768 flop in 32 cycles) at the clock the
+    device reports."""
+    from pytensor_amd.dispatch.elemwise import _StreamEnv, _cast
+
+    khz = C.c_int()
+    assert C.CDLL("libamdhip64.so").hipDeviceGetAttribute(C.byref(khz), 5, 0) == 0  # hipDeviceAttributeClockRate
+    mhz = khz.value / 1e3
+    peak = 256 * 4 * 1024 * mhz * 1e6 / 1e12
+    env = _StreamEnv()
+    rng = np.random.default_rng(0)
+    f32 = ffi.np_dtype_code("float32")
+    for batch, M, N, K in HALF_SHAPES:
+        A = DeviceArray.from_host(rng.standard_normal((batch, M, K)).astype(np.float16))
+        B = DeviceArray.from_host(rng.standard_normal((batch, K, N)).astype(np.float16))
+        out = DeviceArray.empty((batch, M, N), "float16")
+        for tag, tA, tB in ORIENT:
+            # the same buffers read as the stored transposes: other operand values, the same work
+            (a0, a1), (b0, b1) = ((1, M) if tA else (K, 1)), ((1, K) if tB else (N, 1))
+
+            def half():
+                ffi.check(lib.pthip_hgemm(batch, M, N, K, A.ptr, M * K, a0, a1, B.ptr, K * N, b0, b1, out.ptr))
+
+            def cast_sgemm():
+                A32, B32 = _cast(env, A, "float32"), _cast(env, B, "float32")
+                o32 = DeviceArray.empty((batch, M, N), "float32")
+                ffi.check(lib.pthip_gemm(f32, batch, M, N, K, 1.0, A32.ptr, M * K, a0, a1, B32.ptr, K * N, b0, b1, 0.0, None, 0, 0, 0, o32.ptr))
+                return _cast(env, o32, "float16")
+
+            runs = [(timed(lib, half, 20), timed(lib, cast_sgemm, 20)) for _ in range(2)]
+            ms_h, ms_c = min(r[0] for r in runs), min(r[1] for r in runs)
+            tf = 2.0 * batch * M * N * K / ms_h / 1e9
+            print(json.dumps({"dtype": "float16", "batch": batch, "M": M, "N": N, "K": K, "orient": tag, "hgemm_ms": round(ms_h, 4),
+                              "cast_sgemm_ms": round(ms_c, 4), "speedup": round(ms_c / ms_h, 2), "TFLOPs": round(tf, 1),
+                              "clock_MHz": round(mhz), "peak_TFLOPs": round(peak, 1), "frac": round(tf / peak, 3),
+                              "runs_ms": [[round(v, 4) for v in r] for r in runs]}), flush=True)
+
+
 def main():
     ffi.init(0)
     lib = ffi.lib()
+    if sys.argv[1:] == ["half"]:  # the float16 rows only
+        return half_rows(lib)
     shapes = [
         ("float32", 1, 4096, 4096, 4096), ("float32", 1, 8192, 8192, 1024), ("float32", 512, 256, 256, 256),
         ("float32", 64, 1024, 1024, 256), ("float64", 1, 4096, 4096, 4096), ("float32", 1, 64, 2048, 1024),
