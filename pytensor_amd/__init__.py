@@ -5,6 +5,7 @@ Layout (only what the hot path needs):
 * ``csrc/``      hand-written HIP kernels for gfx950 + the C-ABI (``libpthip.so``)
 * ``csrc/wave_device.h``  wave64 / workgroup primitives shared by the hand-written linear-algebra kernels (lane exchange,
   fixed-tree sums, maxima, arg-max, block scan); ``csrc/reduce_device.h`` is the generated kernels' counterpart
+* ``csrc/scratch.h``  scope guard that owns a function's pool scratch; ``csrc/common.h`` holds the one LDS opt-in helper
 * ``ffi.py``     ctypes binding of ``include/pthip.h`` (fails loudly if the library is missing)
 * ``ir.py``      portable lowered-graph IR
 * ``lower.py``   PyTensor ``FunctionGraph`` → IR (needs PyTensor)

@@ -6,10 +6,13 @@
 #include <cstdio>
 #include <cstring>
 #include <functional>
+#include <mutex>
 #include <string>
+#include <unordered_map>
 #include <vector>
 
 #include "../../include/pthip.h"
+#include "scratch.h"
 
 namespace pthip {
 
@@ -84,6 +87,36 @@ inline int post_launch(const char* what) {
 
 constexpr int kNumCU = 256;  // MI355X
 constexpr int kLdsPerCU = 160 * 1024;  // bytes of LDS per CU (and the most one workgroup can ask for)
+
+// After this returns 0, `kernel` may be launched with up to `bytes` of dynamic LDS.  A launch gets
+// 48 KB without asking; above that the runtime is told once per kernel and size: grants only grow,
+// so a repeat launch, or one that needs less than an earlier one, costs no runtime call.
+inline int lds_opt_in(const void* kernel, size_t bytes) {
+  if (bytes <= 48 * 1024) return 0;
+  static std::mutex mu;
+  static std::unordered_map<const void*, size_t> granted;
+  std::lock_guard<std::mutex> lk(mu);
+  size_t& g = granted[kernel];
+  if (bytes <= g) return 0;
+  PTHIP_CHECK(hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes));
+  g = bytes;
+  return 0;
+}
+
+// *resident <- how many workgroups of `kernel` (`block` threads, `lds` bytes of dynamic LDS) the
+// device holds at once, counting at most `cap_per_cu` per CU: the most a persistent kernel whose
+// workgroups wait on each other may launch.  Opts the kernel in to `lds`.
+inline int resident_workgroups(const void* kernel, int block, size_t lds, int cap_per_cu, int* resident) {
+  if (int r = lds_opt_in(kernel, lds)) return r;
+  int per_cu = 0, dev = 0, cus = 0;
+  PTHIP_CHECK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kernel, block, lds));
+  PTHIP_CHECK(hipGetDevice(&dev));
+  PTHIP_CHECK(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev));
+  if (per_cu > cap_per_cu) per_cu = cap_per_cu;
+  if (per_cu * cus <= 0) return check(hipErrorInvalidValue, "resident_workgroups: kernel does not fit the device");
+  *resident = per_cu * cus;
+  return 0;
+}
 
 // async copies / fills issued by the library: performed now and, while a recorder is attached,
 // kept for replay (host memory involved must outlive the list: the plan's pinned blocks do)

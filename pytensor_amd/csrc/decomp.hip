@@ -608,11 +608,7 @@ template <class T> int geqrf_typed(long long batch, int m, int n, void* A, void*
   const size_t need = (size_t)m * n * sizeof(T);
   if (need <= QR_LDS_MAX && m <= 512 && !qr_no_lds) {
     auto k = geqrf_kernel<T, 512>;
-    static bool attr = false;
-    if (!attr) {
-      PTHIP_CHECK(hipFuncSetAttribute((const void*)k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)QR_LDS_MAX));
-      attr = true;
-    }
+    if (int r = pthip::lds_opt_in((const void*)k, QR_LDS_MAX)) return r;
     PTHIP_KLAUNCH(k, dim3((unsigned)batch), dim3(BLOCK), need, pthip::ctx().stream, (T*)A, (T*)tau, m, n, 1);
     return pthip::post_launch("geqrf(lds)");
   }
@@ -629,11 +625,7 @@ template <class T> int geqp3_typed(long long batch, int m, int n, void* A, void*
   const size_t need = (size_t)m * n * sizeof(T) + vec;
   if (need <= QR_LDS_MAX && m <= 512 && !qr_no_lds) {
     auto k = geqp3_kernel<T, 512>;
-    static bool attr = false;
-    if (!attr) {
-      PTHIP_CHECK(hipFuncSetAttribute((const void*)k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)QR_LDS_MAX));
-      attr = true;
-    }
+    if (int r = pthip::lds_opt_in((const void*)k, QR_LDS_MAX)) return r;
     PTHIP_KLAUNCH(k, dim3((unsigned)batch), dim3(BLOCK), need, pthip::ctx().stream, (T*)A, (T*)tau, (int*)jpvt, m, n, 1);
     return pthip::post_launch("geqp3(lds)");
   }
@@ -641,11 +633,7 @@ template <class T> int geqp3_typed(long long batch, int m, int n, void* A, void*
     return pthip::set_error("pthip_geqp3: n = %d columns: the norm and permutation vectors (%zu bytes) do not fit the LDS (%zu)", n, vec,
                             QP3_VEC_MAX);
   auto k = geqp3_kernel<T, VMAX>;
-  static bool attr = false;
-  if (!attr) {
-    PTHIP_CHECK(hipFuncSetAttribute((const void*)k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)QP3_VEC_MAX));
-    attr = true;
-  }
+  if (int r = pthip::lds_opt_in((const void*)k, QP3_VEC_MAX)) return r;
   PTHIP_KLAUNCH(k, dim3((unsigned)batch), dim3(BLOCK), vec, pthip::ctx().stream, (T*)A, (T*)tau, (int*)jpvt, m, n, 0);
   return pthip::post_launch("geqp3");
 }
@@ -655,11 +643,7 @@ template <class T> int orgqr_typed(long long batch, int m, int nc, int k, const 
   const size_t need = (size_t)m * nc * sizeof(T);
   if (need <= QR_LDS_MAX && m <= 512 && !qr_no_lds) {
     auto kk = orgqr_kernel<T, 512>;
-    static bool attr = false;
-    if (!attr) {
-      PTHIP_CHECK(hipFuncSetAttribute((const void*)kk, hipFuncAttributeMaxDynamicSharedMemorySize, (int)QR_LDS_MAX));
-      attr = true;
-    }
+    if (int r = pthip::lds_opt_in((const void*)kk, QR_LDS_MAX)) return r;
     PTHIP_KLAUNCH(kk, dim3((unsigned)batch), dim3(BLOCK), need, pthip::ctx().stream, (const T*)QR, ldqr, stride, (const T*)tau, (T*)Q, m, nc, k, 1);
     return pthip::post_launch("orgqr(lds)");
   }

@@ -629,10 +629,10 @@ int eigh_block_jacobi(long long n, int lower, const T* A, T* W, T* V) {
   const size_t sbytes = (size_t)npairs * m * m * sizeof(T);
   const size_t ibytes = ((size_t)N * 8 + 255) / 256 * 256;
   const size_t lbytes = ((size_t)N * sizeof(T) + 255) / 256 * 256;
+  pthip::Scratch mem;
   void* ws = nullptr;
-  int r = pthip_alloc(5 * mat + 2 * sbytes + (size_t)npairs * m * sizeof(T) + 256 + 3 * ibytes + lbytes + 256, &ws);
+  int r = mem.alloc(5 * mat + 2 * sbytes + (size_t)npairs * m * sizeof(T) + 256 + 3 * ibytes + lbytes + 256, &ws);
   if (r) return r;
-  auto fail = [&](int rc) { pthip_free(ws); return rc; };
   char* p = (char*)ws;
   T* Gt = (T*)p; p += mat;
   T* G2 = (T*)p; p += mat;
@@ -649,17 +649,17 @@ int eigh_block_jacobi(long long n, int lower, const T* A, T* W, T* V) {
   unsigned long long* maxbits = (unsigned long long*)p;  // [0] ||A||_inf bits, [1] low word: off-diagonal bits, [2] ||A^4||_inf bits
   unsigned* offbits = (unsigned*)(maxbits + 1);
   T* sigma = (T*)(maxbits + 3);
-  if ((r = eigh_tournament_upload(npairs, idx, dst, st))) return fail(r);
-  if (hipError_t e = hipMemsetAsync(maxbits, 0, 32, st); e != hipSuccess) return fail(pthip::check(e, "eigh memset"));
+  if ((r = eigh_tournament_upload(npairs, idx, dst, st))) return r;
+  if (hipError_t e = hipMemsetAsync(maxbits, 0, 32, st); e != hipSuccess) return pthip::check(e, "eigh memset");
   PTHIP_KLAUNCH((eigh_rowsum_kernel<T>), dim3((unsigned)((n + 3) / 4)), dim3(256), 0, st, A, n, lower, maxbits);
   const unsigned pg = (unsigned)(N * N / 256 > 4096 ? 4096 : (N * N + 255) / 256);
   PTHIP_KLAUNCH((eigh_prep_kernel<T>), dim3(pg), dim3(256), 0, st, A, n, N, lower, Gt, Vt);
   // ||A||_2^4 = ||A^4||_2 <= ||A^4||_inf: two squarings on the MFMA GEMM
-  if ((r = pthip_gemm(dt, 1, N, N, N, 1.0, Gt, 0, N, 1, Gt, 0, N, 1, 0.0, nullptr, 0, 0, 0, G2))) return fail(r);
-  if ((r = pthip_gemm(dt, 1, N, N, N, 1.0, G2, 0, N, 1, G2, 0, N, 1, 0.0, nullptr, 0, 0, 0, V2))) return fail(r);
+  if ((r = pthip_gemm(dt, 1, N, N, N, 1.0, Gt, 0, N, 1, Gt, 0, N, 1, 0.0, nullptr, 0, 0, 0, G2))) return r;
+  if ((r = pthip_gemm(dt, 1, N, N, N, 1.0, G2, 0, N, 1, G2, 0, N, 1, 0.0, nullptr, 0, 0, 0, V2))) return r;
   PTHIP_KLAUNCH((eigh_absrow_kernel<T>), dim3((unsigned)((N + 3) / 4)), dim3(256), 0, st, (const T*)V2, N, maxbits + 2);
   PTHIP_KLAUNCH((eigh_shift_kernel<T>), dim3(pg), dim3(256), 0, st, Gt, B, n, N, (const unsigned long long*)maxbits, sigma);
-  if ((r = pthip::post_launch("eigh_prep"))) return fail(r);
+  if ((r = pthip::post_launch("eigh_prep"))) return r;
   const double eps = sizeof(T) == 8 ? 2.220446049250313e-16 : 1.1920929e-07;
   const double tol = eps * (N > 256 ? (double)N / 4 : 64.0);
   double prev = 1e300;
@@ -674,10 +674,10 @@ int eigh_block_jacobi(long long n, int lower, const T* A, T* W, T* V) {
     // G = B V afresh at the start of a sweep: G and V take the same rotations, but their rounding errors are their
     // own — over hundreds of rounds G drifts away from B V (measured: eigenvalues off by 1e2 eps sigma without this)
     if (sweep > 0)
-      if ((r = pthip_gemm(dt, 1, N, N, N, 1.0, Vt, 0, N, 1, B, 0, N, 1, 0.0, nullptr, 0, 0, 0, Gt))) return fail(r);
+      if ((r = pthip_gemm(dt, 1, N, N, N, 1.0, Vt, 0, N, 1, B, 0, N, 1, 0.0, nullptr, 0, 0, 0, Gt))) return r;
     for (long long rd = 0; rd < rounds; rd++) {
       // Gram matrices of the pairs: S_p = G_p^T G_p with G_p^T = rows [p m, (p+1) m) of Gt
-      if ((r = pthip_gemm(dt, npairs, m, m, N, 1.0, Gt, m * N, N, 1, Gt, m * N, 1, N, 0.0, nullptr, 0, 0, 0, S))) return fail(r);
+      if ((r = pthip_gemm(dt, npairs, m, m, N, 1.0, Gt, m * N, N, 1, Gt, m * N, 1, N, 0.0, nullptr, 0, 0, 0, S))) return r;
       PTHIP_KLAUNCH((eigh_offdiag_kernel<T>), dim3((unsigned)(npairs * m * m / 256)), dim3(256), 0, st, (const T*)S, npairs, (int)m, offbits);
       // (inner sweeps are capped: a subproblem need not be diagonalised to the last bit while the pairs around it
       //  are still far from orthogonal; PTHIP_EIGH_INNER overrides)
@@ -692,7 +692,7 @@ int eigh_block_jacobi(long long n, int lower, const T* A, T* W, T* V) {
       // full sweep in every round (round 4).
       static const bool cross_ok = !(getenv("PTHIP_EIGH_CROSS") && atoi(getenv("PTHIP_EIGH_CROSS")) == 0);
       const int cross = (cross_ok && rd > 0 && prev > 1e-3) ? 1 : 0;
-      if ((r = eigh_typed<T>(npairs, m, 1, S, Wsub, U, /*sorted=*/0, inner_cap, cross))) return fail(r);
+      if ((r = eigh_typed<T>(npairs, m, 1, S, Wsub, U, /*sorted=*/0, inner_cap, cross))) return r;
       // G_p <- G_p U  <=>  rows: Gt_p <- U^T Gt_p ; the same for V
       static const bool fused_update = !(getenv("PTHIP_EIGH_FUSED_UPDATE") && atoi(getenv("PTHIP_EIGH_FUSED_UPDATE")) == 0);
       if (fused_update) {
@@ -702,20 +702,20 @@ int eigh_block_jacobi(long long n, int lower, const T* A, T* W, T* V) {
         std::swap(Vt, V2);
         continue;
       }
-      if ((r = pthip_gemm(dt, npairs, m, N, m, 1.0, U, m * m, 1, m, Gt, m * N, N, 1, 0.0, nullptr, 0, 0, 0, G2))) return fail(r);
-      if ((r = pthip_gemm(dt, npairs, m, N, m, 1.0, U, m * m, 1, m, Vt, m * N, N, 1, 0.0, nullptr, 0, 0, 0, V2))) return fail(r);
+      if ((r = pthip_gemm(dt, npairs, m, N, m, 1.0, U, m * m, 1, m, Gt, m * N, N, 1, 0.0, nullptr, 0, 0, 0, G2))) return r;
+      if ((r = pthip_gemm(dt, npairs, m, N, m, 1.0, U, m * m, 1, m, Vt, m * N, N, 1, 0.0, nullptr, 0, 0, 0, V2))) return r;
       if (nbk > 2) {
-        if ((r = pthip_take_rows((int)sizeof(T), N, N, G2, N, N, (const int64_t*)idx, Gt))) return fail(r);
-        if ((r = pthip_take_rows((int)sizeof(T), N, N, V2, N, N, (const int64_t*)idx, Vt))) return fail(r);
+        if ((r = pthip_take_rows((int)sizeof(T), N, N, G2, N, N, (const int64_t*)idx, Gt))) return r;
+        if ((r = pthip_take_rows((int)sizeof(T), N, N, V2, N, N, (const int64_t*)idx, Vt))) return r;
       } else {
         std::swap(Gt, G2);
         std::swap(Vt, V2);
       }
     }
     unsigned hb = 0;
-    if (hipError_t e = hipMemcpyAsync(&hb, offbits, 4, hipMemcpyDeviceToHost, st); e != hipSuccess) return fail(pthip::check(e, "eigh off-diagonal read"));
-    if (hipError_t e = hipStreamSynchronize(st); e != hipSuccess) return fail(pthip::check(e, "eigh sweep sync"));
-    if (hipError_t e = hipMemsetAsync(offbits, 0, 4, st); e != hipSuccess) return fail(pthip::check(e, "eigh memset"));
+    if (hipError_t e = hipMemcpyAsync(&hb, offbits, 4, hipMemcpyDeviceToHost, st); e != hipSuccess) return pthip::check(e, "eigh off-diagonal read");
+    if (hipError_t e = hipStreamSynchronize(st); e != hipSuccess) return pthip::check(e, "eigh sweep sync");
+    if (hipError_t e = hipMemsetAsync(offbits, 0, 4, st); e != hipSuccess) return pthip::check(e, "eigh memset");
     float offf;
     memcpy(&offf, &hb, 4);
     const double off = offf;
@@ -728,13 +728,11 @@ int eigh_block_jacobi(long long n, int lower, const T* A, T* W, T* V) {
     // (scipy raises LinAlgError when LAPACK reports non-convergence: bit 3 of the device error word)
     PTHIP_KLAUNCH(eigh_status_or_kernel, dim3(1), dim3(1), 0, st, (int*)pthip_status_ptr(), 8);
   }
-  if ((r = pthip_gemm(dt, 1, N, N, N, 1.0, Vt, 0, N, 1, B, 0, N, 1, 0.0, nullptr, 0, 0, 0, Gt))) return fail(r);  // lambda from a fresh B V
+  if ((r = pthip_gemm(dt, 1, N, N, N, 1.0, Vt, 0, N, 1, B, 0, N, 1, 0.0, nullptr, 0, 0, 0, Gt))) return r;  // lambda from a fresh B V
   PTHIP_KLAUNCH((eigh_lambda_kernel<T>), dim3((unsigned)((N + 3) / 4)), dim3(256), 0, st, (const T*)Gt, (const T*)Vt, N, (const T*)sigma, lam);
   PTHIP_KLAUNCH((eigh_rank_kernel<T>), dim3((unsigned)((N + 255) / 256)), dim3(256), 0, st, (const T*)lam, N, n, rank, W);
   PTHIP_KLAUNCH((eigh_scatter_kernel<T>), dim3((unsigned)((n + 255) / 256), (unsigned)N), dim3(256), 0, st, (const T*)Vt, (const int*)rank, N, n, V);
-  r = pthip::post_launch("eigh_block_finish");
-  pthip_free(ws);
-  return r;
+  return pthip::post_launch("eigh_block_finish");
 }
 
 template <class T>
@@ -758,11 +756,7 @@ int eigh_typed(long long batch, long long n, int lower, const void* A, void* W, 
   //  outside its 1e-5 for the small eigenvalues in fp32, where A and V both fit the LDS up to n = 136 anyway)
   if (sizeof(T) == 8 && sorted && !two_sided && n >= 8 && n <= EIGH1_MAXN && n <= 16 * EIGH1_UP && one <= 160 * 1024 - 8 * 1024) {
     auto k1 = eigh_onesided_kernel<T>;
-    static bool attr1 = false;
-    if (!attr1) {
-      PTHIP_CHECK(hipFuncSetAttribute((const void*)k1, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024 - 8 * 1024));
-      attr1 = true;
-    }
+    if (int r = pthip::lds_opt_in((const void*)k1, 160 * 1024 - 8 * 1024)) return r;
     PTHIP_KLAUNCH(k1, dim3((unsigned)batch), dim3(EIGH1_BLOCK), one, st, (const T*)A, (T*)W, (T*)V, (int)n, lower, (int*)pthip_status_ptr());
     return pthip::post_launch("eigh(one-sided)");
   }
@@ -775,18 +769,15 @@ int eigh_typed(long long batch, long long n, int lower, const void* A, void* W, 
   static const bool inner_wide = !(getenv("PTHIP_EIGH_INNER_WIDE") && atoi(getenv("PTHIP_EIGH_INNER_WIDE")) == 0);
   const bool wide = n > 64 || (inner_wide && !sorted && batch <= 256);
   auto k = wide ? eigh_jacobi_kernel<T, 1024> : eigh_jacobi_kernel<T, 256>;
-  if (dyn > 48 * 1024)
-    PTHIP_CHECK(hipFuncSetAttribute((const void*)k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)dyn));
+  if (int r = pthip::lds_opt_in((const void*)k, dyn)) return r;
+  pthip::Scratch mem;
   void *sa = nullptr, *sv = nullptr;
-  if (!a_lds) { int r = pthip_alloc((size_t)batch * one, &sa); if (r) return r; }
-  if (!v_lds) { int r = pthip_alloc((size_t)batch * one, &sv); if (r) { if (sa) pthip_free(sa); return r; } }
+  if (!a_lds) { int r = mem.alloc((size_t)batch * one, &sa); if (r) return r; }
+  if (!v_lds) { int r = mem.alloc((size_t)batch * one, &sv); if (r) return r; }
   PTHIP_KLAUNCH(k, dim3((unsigned)batch), dim3(wide ? 1024 : 256), dyn, st, (const T*)A, (T*)W, (T*)V, (int)n, lower,
                      a_lds ? 1 : 0, v_lds ? 1 : 0, (T*)sa, (T*)sv, (int*)pthip_status_ptr(), sorted, max_sweeps, (cross && n % 2 == 0) ? 1 : 0,
                      rel_only);
-  int r = pthip::post_launch("eigh");
-  if (sa) pthip_free(sa);  // stream-ordered reuse keeps this safe
-  if (sv) pthip_free(sv);
-  return r;
+  return pthip::post_launch("eigh");
 }
 
 // ------------------------------------------------------------------------------------------
@@ -937,25 +928,23 @@ int svd_block_complete(long long c, long long kv, long long rows_out, T* Wt) {
   hipStream_t st = pthip::ctx().stream;
   const int dt = sizeof(T) == 8 ? PTHIP_F64 : PTHIP_F32;
   const size_t mat = ((size_t)c * c * sizeof(T) + 255) / 256 * 256;
+  pthip::Scratch mem;
   void* ws = nullptr;
-  int r = pthip_alloc(3 * mat + (size_t)c * sizeof(T), &ws);
+  int r = mem.alloc(3 * mat + (size_t)c * sizeof(T), &ws);
   if (r) return r;
-  auto fail = [&](int rc) { pthip_free(ws); return rc; };
   T* Eye = (T*)ws;
   T* Cm = (T*)((char*)ws + mat);
   T* V = (T*)((char*)ws + 2 * mat);
   T* W = (T*)((char*)ws + 3 * mat);
   PTHIP_KLAUNCH((svdb_eye_kernel<T>), dim3(svdb_grid(c * c)), dim3(256), 0, st, kv > 0 ? Eye : Cm, c);
-  if ((r = pthip::post_launch("svd_block_eye"))) return fail(r);
+  if ((r = pthip::post_launch("svd_block_eye"))) return r;
   // C = I - Wt^T Wt over the valid rows: an orthogonal projector, eigenvalue 0 (kv times) and 1
   if (kv > 0)
-    if ((r = pthip_gemm(dt, 1, c, c, kv, -1.0, Wt, 0, 1, c, Wt, 0, c, 1, 1.0, Eye, 0, c, 1, Cm))) return fail(r);
-  if ((r = eigh_typed<T>(1, c, 1, Cm, W, V))) return fail(r);
+    if ((r = pthip_gemm(dt, 1, c, c, kv, -1.0, Wt, 0, 1, c, Wt, 0, c, 1, 1.0, Eye, 0, c, 1, Cm))) return r;
+  if ((r = eigh_typed<T>(1, c, 1, Cm, W, V))) return r;
   const long long count = rows_out - kv;
   PTHIP_KLAUNCH((svdb_complete_kernel<T>), dim3(svdb_grid(count * c)), dim3(256), 0, st, (const T*)V, c, kv, count, Wt);
-  r = pthip::post_launch("svd_block_complete");
-  pthip_free(ws);
-  return r;
+  return pthip::post_launch("svd_block_complete");
 }
 
 template <class T>
@@ -968,10 +957,10 @@ int svd_block_item(long long r, long long c, int vectors, long long rows_out, co
   const size_t xbytes = (size_t)N * LDC * sizeof(T), pbytes = vectors ? (size_t)N * N * sizeof(T) : 0;
   const size_t sbytes = (size_t)npairs * m * m * sizeof(T);
   const size_t ibytes = ((size_t)N * 8 + 255) / 256 * 256;
+  pthip::Scratch mem;
   void* ws = nullptr;
-  int rc = pthip_alloc(2 * xbytes + 2 * pbytes + 2 * sbytes + 4 * ibytes + 256, &ws);
+  int rc = mem.alloc(2 * xbytes + 2 * pbytes + 2 * sbytes + 4 * ibytes + 256, &ws);
   if (rc) return rc;
-  auto fail = [&](int e) { pthip_free(ws); return e; };
   char* p = (char*)ws;
   T* X = (T*)p; p += xbytes;
   T* X2 = (T*)p; p += xbytes;
@@ -988,12 +977,12 @@ int svd_block_item(long long r, long long c, int vectors, long long rows_out, co
   int* bad = (int*)(offbits + 1);
   int* nzero = bad + 1;
   svdb_last_sweeps = 0;
-  if (hipError_t e = hipMemsetAsync(maxbits, 0, 32, st); e != hipSuccess) return fail(pthip::check(e, "svd_block memset"));
+  if (hipError_t e = hipMemsetAsync(maxbits, 0, 32, st); e != hipSuccess) return pthip::check(e, "svd_block memset");
   PTHIP_KLAUNCH((svdb_absmax_kernel<T>), dim3(svdb_grid(r * c)), dim3(256), 0, st, Xin, r * c, maxbits, bad);
-  if ((rc = pthip::post_launch("svd_block_absmax"))) return fail(rc);
+  if ((rc = pthip::post_launch("svd_block_absmax"))) return rc;
   unsigned long long head[2] = {0, 0};
-  if (hipError_t e = hipMemcpyAsync(head, maxbits, 16, hipMemcpyDeviceToHost, st); e != hipSuccess) return fail(pthip::check(e, "svd_block scale read"));
-  if (hipError_t e = hipStreamSynchronize(st); e != hipSuccess) return fail(pthip::check(e, "svd_block scale sync"));
+  if (hipError_t e = hipMemcpyAsync(head, maxbits, 16, hipMemcpyDeviceToHost, st); e != hipSuccess) return pthip::check(e, "svd_block scale read");
+  if (hipError_t e = hipStreamSynchronize(st); e != hipSuccess) return pthip::check(e, "svd_block scale sync");
   int hbad;
   memcpy(&hbad, (char*)head + 12, 4);
   if (hbad) {
@@ -1006,9 +995,7 @@ int svd_block_item(long long r, long long c, int vectors, long long rows_out, co
       PTHIP_KLAUNCH((svdb_fill_kernel<T>), dim3(svdb_grid(r * r)), dim3(256), 0, st, Pout, r * r, nan);
     }
     PTHIP_KLAUNCH(eigh_status_or_kernel, dim3(1), dim3(1), 0, st, (int*)pthip_status_ptr(), 4);
-    rc = pthip::post_launch("svd_block_nonfinite");
-    pthip_free(ws);
-    return rc;
+    return pthip::post_launch("svd_block_nonfinite");
   }
   double amax;
   memcpy(&amax, head, 8);
@@ -1017,9 +1004,9 @@ int svd_block_item(long long r, long long c, int vectors, long long rows_out, co
   const int elim = sizeof(T) == 8 ? 1000 : 120;  // (the scale itself must be a normal number of T)
   const int sh = 1 - ex > elim ? elim : (1 - ex < -elim ? -elim : 1 - ex);
   const T scale = (T)ldexp(1.0, sh);
-  if ((rc = eigh_tournament_upload(npairs, nullptr, dst, st))) return fail(rc);
+  if ((rc = eigh_tournament_upload(npairs, nullptr, dst, st))) return rc;
   PTHIP_KLAUNCH((svdb_prep_kernel<T>), dim3(svdb_grid(N * (LDC > N ? LDC : N))), dim3(256), 0, st, Xin, r, c, N, LDC, scale, X, Pt);
-  if ((rc = pthip::post_launch("svd_block_prep"))) return fail(rc);
+  if ((rc = pthip::post_launch("svd_block_prep"))) return rc;
   const double eps = sizeof(T) == 8 ? 2.220446049250313e-16 : 1.1920929e-07;
   // the Gram matrices carry a rounding error of order eps sqrt(row length): a threshold of the bare eps would rotate a
   // pair back and forth for ever (DESIGN §4 "Batched SVD")
@@ -1030,20 +1017,20 @@ int svd_block_item(long long r, long long c, int vectors, long long rows_out, co
   for (int sweep = 0; sweep < SVDB_MAX_SWEEPS && !converged; sweep++) {
     const long long rounds = nbk > 2 ? nbk - 1 : 1;
     for (long long rd = 0; rd < rounds; rd++) {
-      if ((rc = pthip_gemm(dt, npairs, m, m, LDC, 1.0, X, m * LDC, LDC, 1, X, m * LDC, 1, LDC, 0.0, nullptr, 0, 0, 0, Sg))) return fail(rc);
+      if ((rc = pthip_gemm(dt, npairs, m, m, LDC, 1.0, X, m * LDC, LDC, 1, X, m * LDC, 1, LDC, 0.0, nullptr, 0, 0, 0, Sg))) return rc;
       PTHIP_KLAUNCH((eigh_offdiag_kernel<T>), dim3((unsigned)(npairs * m * m / 256)), dim3(256), 0, st, (const T*)Sg, npairs, (int)m, offbits);
       // (one inner sweep; cross pairs only after the sweep's first round while far from done: see eigh_block_jacobi)
       const int cross = (rd > 0 && prev > 1e-3) ? 1 : 0;
-      if ((rc = eigh_typed<T>(npairs, m, 1, Sg, Wsub, U, /*sorted=*/0, /*max_sweeps=*/1, cross, /*rel_only=*/1))) return fail(rc);
+      if ((rc = eigh_typed<T>(npairs, m, 1, Sg, Wsub, U, /*sorted=*/0, /*max_sweeps=*/1, cross, /*rel_only=*/1))) return rc;
       PTHIP_KLAUNCH((eigh_pair_update_kernel<T>), dim3((unsigned)((LDC > N ? LDC : N) / m), (unsigned)npairs, vectors ? 2u : 1u), dim3(256), 0, st,
                     (const T*)U, (const T*)X, (const T*)Pt, X2, P2, LDC, N, (const long long*)dst);
       std::swap(X, X2);
       std::swap(Pt, P2);
     }
     unsigned hb = 0;
-    if (hipError_t e = hipMemcpyAsync(&hb, offbits, 4, hipMemcpyDeviceToHost, st); e != hipSuccess) return fail(pthip::check(e, "svd_block off-diagonal read"));
-    if (hipError_t e = hipStreamSynchronize(st); e != hipSuccess) return fail(pthip::check(e, "svd_block sweep sync"));
-    if (hipError_t e = hipMemsetAsync(offbits, 0, 4, st); e != hipSuccess) return fail(pthip::check(e, "svd_block memset"));
+    if (hipError_t e = hipMemcpyAsync(&hb, offbits, 4, hipMemcpyDeviceToHost, st); e != hipSuccess) return pthip::check(e, "svd_block off-diagonal read");
+    if (hipError_t e = hipStreamSynchronize(st); e != hipSuccess) return pthip::check(e, "svd_block sweep sync");
+    if (hipError_t e = hipMemsetAsync(offbits, 0, 4, st); e != hipSuccess) return pthip::check(e, "svd_block memset");
     float offf;
     memcpy(&offf, &hb, 4);
     const double off = offf;
@@ -1054,18 +1041,14 @@ int svd_block_item(long long r, long long c, int vectors, long long rows_out, co
   if (!converged) PTHIP_KLAUNCH(eigh_status_or_kernel, dim3(1), dim3(1), 0, st, (int*)pthip_status_ptr(), 4);  // bit 2: "SVD did not converge"
   PTHIP_KLAUNCH((svdb_norm_kernel<T>), dim3((unsigned)((N + 3) / 4)), dim3(256), 0, st, (const T*)X, N, LDC, c, lam);
   PTHIP_KLAUNCH((svdb_rank_kernel<T>), dim3((unsigned)((N + 255) / 256)), dim3(256), 0, st, (const T*)lam, N, r, scale, rank, S, nzero);
-  if (!vectors) {
-    rc = pthip::post_launch("svd_block_finish");
-    pthip_free(ws);
-    return rc;
-  }
+  if (!vectors) return pthip::post_launch("svd_block_finish");
   PTHIP_KLAUNCH((svdb_scatter_kernel<T>), dim3((unsigned)((c + 255) / 256), (unsigned)N), dim3(256), 0, st, (const T*)X, (const T*)Pt, (const T*)lam,
                 (const int*)rank, N, LDC, r, c, Wt, Pout);
-  if ((rc = pthip::post_launch("svd_block_finish"))) return fail(rc);
+  if ((rc = pthip::post_launch("svd_block_finish"))) return rc;
   int hz = 0;
-  if (hipError_t e = hipMemcpyAsync(&hz, nzero, 4, hipMemcpyDeviceToHost, st); e != hipSuccess) return fail(pthip::check(e, "svd_block zero count read"));
-  if (hipError_t e = hipStreamSynchronize(st); e != hipSuccess) return fail(pthip::check(e, "svd_block finish sync"));
-  pthip_free(ws);
+  if (hipError_t e = hipMemcpyAsync(&hz, nzero, 4, hipMemcpyDeviceToHost, st); e != hipSuccess) return pthip::check(e, "svd_block zero count read");
+  if (hipError_t e = hipStreamSynchronize(st); e != hipSuccess) return pthip::check(e, "svd_block finish sync");
+  mem.release();  // (before svd_block_complete takes its own scratch: the two need not be live together)
   if (hz < 0 || hz > r) return pthip::set_error("pthip_svd_block: %d zero singular values of %lld", hz, r);
   if (rows_out > r || hz > 0) return svd_block_complete<T>(c, r - hz, rows_out, Wt);
   return 0;

@@ -369,11 +369,7 @@ int gbsv_typed(long long batch, long long n, long long nrhs, const void* A, long
                             (size_t)batch * n * n * sizeof(T));
   const size_t lds = worst < GB_LDS_MAX ? (worst + 15) / 16 * 16 : GB_LDS_MAX;
   auto k = gbsv_kernel<T>;
-  static bool attr = false;
-  if (!attr) {
-    PTHIP_CHECK(hipFuncSetAttribute((const void*)k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)GB_LDS_MAX));
-    attr = true;
-  }
+  if (int r = pthip::lds_opt_in((const void*)k, GB_LDS_MAX)) return r;
   PTHIP_KLAUNCH(k, dim3((unsigned)batch), dim3(WG), lds, pthip::ctx().stream, (int)n, nrhs, (const T*)A, sAb, sA0, sA1, (const T*)B, sBb, (T*)X,
                 band, worst > GB_LDS_MAX ? (T*)ws : (T*)nullptr, (unsigned)lds);
   return pthip::post_launch("gbsv_batched");

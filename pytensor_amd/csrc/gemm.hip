@@ -894,11 +894,7 @@ int launch(long long batch, long long M, long long N, long long K, T alpha, cons
   using SB = Stage<T, BKC, BKT>;
   const size_t shmem = (size_t)(2 * SA::SIZE + 2 * SB::SIZE) * sizeof(T);
   auto k = KernelSel<T>::template get<AKC, BKC, SKINNY, BKT>();
-  static bool attr_set = false;
-  if (!attr_set && shmem > 64 * 1024) {
-    PTHIP_CHECK(hipFuncSetAttribute((const void*)k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)shmem));
-    attr_set = true;
-  }
+  if (int r = pthip::lds_opt_in((const void*)k, shmem)) return r;
   const long long tiles_m = (M + BM - 1) / BM, tiles_n = (N + BN - 1) / BN;
   constexpr int VN = 16 / sizeof(T);
   const int vecA = (lda % VN == 0) && (((uintptr_t)A) % 16 == 0) && (sAb % VN == 0);
@@ -939,11 +935,7 @@ int launch(long long batch, long long M, long long N, long long K, T alpha, cons
         const size_t sh = (size_t)(2 * (AKC ? T2 * T2ALD : T2K * T2) + 2 * (BKC ? T2 * T2ALD : T2K * T2)) * sizeof(float);
         static const bool pf = !(getenv("PTHIP_SGEMM_256_PF") && atoi(getenv("PTHIP_SGEMM_256_PF")) == 0);
         auto k256 = pf ? sgemm256_kernel<true, AKC, BKC> : sgemm256_kernel<false, AKC, BKC>;
-        static bool attr_b = false;
-        if (!attr_b) {
-          PTHIP_CHECK(hipFuncSetAttribute((const void*)k256, hipFuncAttributeMaxDynamicSharedMemorySize, (int)pthip::kLdsPerCU));
-          attr_b = true;
-        }
+        if (int r = pthip::lds_opt_in((const void*)k256, pthip::kLdsPerCU)) return r;
         const long long t_m = M / T2, t_n = N / T2, tot = t_m * t_n * batch;
         // Experiment switches for a product enqueued on a side stream (the hoisted sequence product of a Scan, one chunk
         // ahead of the steps that read it: dispatch/blas.py LazySeq, PTHIP_SCAN_OVERLAP=1): PTHIP_SIDE_GEMM_WGS caps its
@@ -969,14 +961,10 @@ int launch(long long batch, long long M, long long N, long long K, T alpha, cons
       static const bool persist = !(getenv("PTHIP_SGEMM_PERSIST") && atoi(getenv("PTHIP_SGEMM_PERSIST")) == 0);
       const long long total = tiles_m * tiles_n * batch, resident = (long long)pthip::kNumCU * 2;
       if (persist && total > resident) {
-        static bool attr_p = false;
         static const int diag = getenv("PTHIP_SGEMM_DIAG") ? atoi(getenv("PTHIP_SGEMM_DIAG")) : 0;
         auto kp = diag == 1 ? sgemm_persistent_kernel<AKC, BKC, 1> : diag == 2 ? sgemm_persistent_kernel<AKC, BKC, 2>
                   : diag == 3 ? sgemm_persistent_kernel<AKC, BKC, 3> : sgemm_persistent_kernel<AKC, BKC, 0>;
-        if (!attr_p && shmem > 64 * 1024) {
-          PTHIP_CHECK(hipFuncSetAttribute((const void*)kp, hipFuncAttributeMaxDynamicSharedMemorySize, (int)shmem));
-          attr_p = true;
-        }
+        if (int r = pthip::lds_opt_in((const void*)kp, shmem)) return r;
         PTHIP_KLAUNCH(kp, dim3((unsigned)resident), dim3(BLOCK), shmem, st, (float*)out, (const float*)A, (const float*)B,
                       (const float*)C, M, N, K, lda, ldb, sAb, sBb, sCb, sC0, sC1, (float)alpha, (float)beta, tiles_m, tiles_n,
                       vecA, vecB, batch, ldo);
@@ -988,21 +976,18 @@ int launch(long long batch, long long M, long long N, long long K, T alpha, cons
     return pthip::post_launch("gemm");
   }
   const long long total = batch * M * N;
+  pthip::Scratch mem;
   void* part = nullptr;
-  int r = pthip_alloc((size_t)nsplit * total * sizeof(T), &part);
+  int r = mem.alloc((size_t)nsplit * total * sizeof(T), &part);
   if (r) return r;
   PTHIP_KLAUNCH(k, grid, dim3(BLOCK), shmem, st, (T*)part, A, B, C, M, N, K, lda, ldb, sAb, sBb,
                      sCb, sC0, sC1, alpha, beta, tiles_m, tiles_n, vecA, vecB, kchunk, N);
-  r = pthip::post_launch("gemm(split-K)");
-  if (!r) {
-    long long blocks = (total + BLOCK - 1) / BLOCK;
-    if (blocks > 2048) blocks = 2048;
-    PTHIP_KLAUNCH((splitk_finish_kernel<T>), dim3((unsigned)blocks), dim3(BLOCK), 0, st, out,
-                       (const T*)part, C, M, N, total, (int)nsplit, sCb, sC0, sC1, alpha, beta, ldo);
-    r = pthip::post_launch("gemm splitk_finish");
-  }
-  pthip_free(part);  // stream-ordered reuse keeps this safe
-  return r;
+  if ((r = pthip::post_launch("gemm(split-K)"))) return r;
+  long long blocks = (total + BLOCK - 1) / BLOCK;
+  if (blocks > 2048) blocks = 2048;
+  PTHIP_KLAUNCH((splitk_finish_kernel<T>), dim3((unsigned)blocks), dim3(BLOCK), 0, st, out,
+                     (const T*)part, C, M, N, total, (int)nsplit, sCb, sC0, sC1, alpha, beta, ldo);
+  return pthip::post_launch("gemm splitk_finish");
 }
 
 // fp32, M > 64: K extent of the staged tiles.  32 = half as many barrier intervals per tile (the

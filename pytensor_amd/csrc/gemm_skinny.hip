@@ -252,20 +252,11 @@ __global__ __launch_bounds__(BLOCK) void skinny_finish_kernel(T* __restrict__ ou
   }
 }
 
-template <class K> int raise_lds(K kernel, size_t bytes, size_t* have) {
-  if (bytes > *have && bytes > 48 * 1024) {
-    PTHIP_CHECK(hipFuncSetAttribute((const void*)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes));
-    *have = bytes;
-  }
-  return 0;
-}
-
 template <class T, int V, int NC>
 int launch_fwd(long long M, int N, int K, double alpha, const T* A, long long lda, const T* B, long long sB0, long long sB1, double beta,
                const T* C, long long sC0, long long sC1, T* out) {
-  static size_t have = 0;
   const size_t lds = ((size_t)TR * (KC + 1) + (size_t)KC * 4 * NC) * sizeof(T);
-  int r = raise_lds(skinny_fwd_kernel<T, V, NC>, lds, &have);
+  int r = pthip::lds_opt_in((const void*)skinny_fwd_kernel<T, V, NC>, lds);
   if (r) return r;
   const long long tiles = (M + TR - 1) / TR;
   long long grid = tiles;
@@ -278,10 +269,9 @@ int launch_fwd(long long M, int N, int K, double alpha, const T* A, long long ld
 
 template <class T, int V, int MJ, int NC>
 int launch_atb(long long rows, int M, int N, const T* X, long long ldx, const T* W, long long ldw, T* slab, int nblocks, long long rows_per_block, int tr) {
-  static size_t have = 0;
   const int MP = (M + V - 1) / V * V;
   const size_t lds = ((size_t)tr * MP + (size_t)tr * 2 * NC) * sizeof(T);
-  int r = raise_lds(skinny_atb_kernel<T, V, MJ, NC>, lds, &have);
+  int r = pthip::lds_opt_in((const void*)skinny_atb_kernel<T, V, MJ, NC>, lds);
   if (r) return r;
   PTHIP_KLAUNCH((skinny_atb_kernel<T, V, MJ, NC>), dim3((unsigned)nblocks), dim3(BLOCK), lds, pthip::ctx().stream, slab, X, ldx, W, ldw, rows, M, N, tr,
                 rows_per_block);
@@ -332,8 +322,9 @@ int skinny_typed(long long M, long long N, long long K, double alpha, const T* A
     long long rpb = (rows + nblocks - 1) / nblocks;
     rpb = (rpb + tr - 1) / tr * tr;
     nblocks = (rows + rpb - 1) / rpb;
+    pthip::Scratch mem;
     void* scratch = nullptr;
-    int r = pthip_alloc((size_t)nblocks * Mi * Ni * sizeof(T), &scratch);
+    int r = mem.alloc((size_t)nblocks * Mi * Ni * sizeof(T), &scratch);
     if (r) return r;
     T* slab = (T*)scratch;
 #define ATB(V, MJ_, NC) r = launch_atb<T, V, MJ_, NC>(rows, Mi, Ni, A, sA1, B, sB0, slab, (int)nblocks, rpb, tr)
@@ -350,14 +341,11 @@ int skinny_typed(long long M, long long N, long long K, double alpha, const T* A
     }
 #undef ATB_MJ
 #undef ATB
-    if (!r) {
-      const int MN = Mi * Ni;
-      PTHIP_KLAUNCH((skinny_finish_kernel<T>), dim3((unsigned)((MN + 15) / 16)), dim3(BLOCK), 0, pthip::ctx().stream, out, (const T*)slab, (int)nblocks,
-                    MN, Ni, C, sC0, sC1, (T)alpha, (T)(C ? beta : 0.0));
-      r = pthip::post_launch("gemm(skinny transposed, finish)");
-    }
-    const int rf = pthip_free(scratch);  // stream-ordered reuse keeps this safe
-    return r ? r : rf;
+    if (r) return r;
+    const int MN = Mi * Ni;
+    PTHIP_KLAUNCH((skinny_finish_kernel<T>), dim3((unsigned)((MN + 15) / 16)), dim3(BLOCK), 0, pthip::ctx().stream, out, (const T*)slab, (int)nblocks,
+                  MN, Ni, C, sC0, sC1, (T)alpha, (T)(C ? beta : 0.0));
+    return pthip::post_launch("gemm(skinny transposed, finish)");
   }
   return 0;
 }

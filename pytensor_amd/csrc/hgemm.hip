@@ -244,11 +244,7 @@ int hgemm_launch(long long batch, long long M, long long N, long long K, const h
   constexpr int TM = SKINNY ? 64 : 128;
   auto k = hgemm_kernel<AKC, BKC, SKINNY>;
   const size_t shmem = (size_t)(2 * HStage<AKC, TM>::SIZE + 2 * HStage<BKC, HN>::SIZE) * sizeof(hbits);
-  static bool attr_set = false;
-  if (!attr_set && shmem > 64 * 1024) {
-    PTHIP_CHECK(hipFuncSetAttribute((const void*)k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)shmem));
-    attr_set = true;
-  }
+  if (int r = pthip::lds_opt_in((const void*)k, shmem)) return r;
   const long long tiles_m = (M + TM - 1) / TM, tiles_n = (N + HN - 1) / HN, total = tiles_m * tiles_n * batch;
   const long long resident = (long long)pthip::kNumCU * 2;
   const long long grid = total < resident ? total : resident;

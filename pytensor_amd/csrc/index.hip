@@ -667,11 +667,8 @@ int pthip_scatter_rows(int dtype, int inc, int64_t n_idx, int64_t inner, void* o
     if (n_bins <= LDS_BINS && n >= 16 * n_bins) {
       auto kl = scatter_add_exact_kernel<true>;
       const size_t sh = (size_t)n_bins * 16;
-      static size_t sh_set = 0;
-      if (sh > sh_set && sh > 48 * 1024) {
-        PTHIP_CHECK(hipFuncSetAttribute((const void*)kl, hipFuncAttributeMaxDynamicSharedMemorySize, (int)(LDS_BINS * 16)));
-        sh_set = LDS_BINS * 16;
-      }
+      if (sh > 48 * 1024)
+        if (int r = pthip::lds_opt_in((const void*)kl, LDS_BINS * 16)) return r;
       // (one workgroup per CU at most: every workgroup ends with up to n_bins pairs of global atomics)
       long long wgs = (n + 16 * BLOCK - 1) / (16 * BLOCK);
       if (wgs > pthip::kNumCU) wgs = pthip::kNumCU;

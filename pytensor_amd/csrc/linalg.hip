@@ -26,6 +26,8 @@
 // Larger matrices: blocked right-looking factorisation over HBM (chol_blocked: LDS-resident
 // diagonal blocks, multi-workgroup panel solves, trailing updates on the MFMA GEMM).
 // Batches (Blockwise) map to grid.x.
+#include <climits>
+
 #include "common.h"
 
 namespace {
@@ -1252,39 +1254,27 @@ int chol_dag(int lower, long long n, const T* A, T* L) {
   const size_t wbytes = direct ? 0 : (size_t)np * np * sizeof(T);
   const size_t dbytes = (size_t)nT * 4 * 16 * 16 * sizeof(T);
   const size_t fbytes = ((size_t)nT * nT * sizeof(int) + 255) / 256 * 256 + 256;
+  pthip::Scratch mem;
   void* scratch = nullptr;
-  int r = pthip_alloc(wbytes + dbytes + fbytes, &scratch);
+  int r = mem.alloc(wbytes + dbytes + fbytes, &scratch);
   if (r) return r;
   T* W = direct ? L : (T*)scratch;
   T* Dinv = (T*)((char*)scratch + wbytes);
   int* flags = (int*)((char*)scratch + wbytes + dbytes);
   int* failflag = flags, *abortflag = flags + 1, *done = flags + 64;
-  auto fail = [&](int rc) { pthip_free(scratch); return rc; };
   auto kk = chol_dag_kernel<T>;
   const size_t lds = (size_t)((2 * DT + 16) * DLS + 4 * 16 * 17 + DT + 64) * sizeof(T);
   static int resident = 0;  // workgroups of this kernel the device holds at once
-  if (!resident) {
-    if (lds > 64 * 1024)
-      if (hipError_t e = hipFuncSetAttribute((const void*)kk, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds); e != hipSuccess)
-        return fail(pthip::check(e, "chol_dag attribute"));
-    int per_cu = 0, dev = 0, cus = 0;
-    if (hipError_t e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, (const void*)kk, BLOCK, lds); e != hipSuccess)
-      return fail(pthip::check(e, "chol_dag occupancy"));
-    if (hipError_t e = hipGetDevice(&dev); e != hipSuccess) return fail(pthip::check(e, "chol_dag device"));
-    if (hipError_t e = hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev); e != hipSuccess)
-      return fail(pthip::check(e, "chol_dag device attribute"));
-    if (per_cu > 2) per_cu = 2;
-    resident = per_cu * cus;
-    if (resident <= 0) return fail(pthip::check(hipErrorInvalidValue, "chol_dag: kernel does not fit the device"));
-  }
-  if (hipError_t e = pthip::memset_async(flags, 0, fbytes, st); e != hipSuccess) return fail(pthip::check(e, "chol flags memset"));
+  if (!resident)
+    if ((r = pthip::resident_workgroups((const void*)kk, BLOCK, lds, 2, &resident))) return r;
+  if (hipError_t e = pthip::memset_async(flags, 0, fbytes, st); e != hipSuccess) return pthip::check(e, "chol flags memset");
   const unsigned ntile = (unsigned)(np / 32);
   if (direct) {
     PTHIP_KLAUNCH((zero_upper_kernel<T>), dim3(ntile, ntile), dim3(BLOCK), 0, st, L, (int)n);
-    if ((r = pthip::post_launch("chol zero upper"))) return fail(r);
+    if ((r = pthip::post_launch("chol zero upper"))) return r;
   } else {
     PTHIP_KLAUNCH((chol_stage_kernel<T>), dim3(ntile, ntile), dim3(BLOCK), 0, st, W, A, (int)n, lower, (int)np);
-    if ((r = pthip::post_launch("chol_stage"))) return fail(r);
+    if ((r = pthip::post_launch("chol_stage"))) return r;
   }
   int ntasks = 0;  // per column: the head task + the tiles from two below the diagonal down
   for (int j = 0; j < nT; j++) ntasks += 1 + ((nT - j - 2) > 0 ? (nT - j - 2) : 0);
@@ -1293,7 +1283,7 @@ int chol_dag(int lower, long long n, const T* A, T* L) {
   static const char* trace_path = getenv("PTHIP_CHOL_TRACE");
   if (trace_path && hipMalloc((void**)&trace, (size_t)ntasks * 16 * sizeof(long long)) != hipSuccess) trace = nullptr;
   PTHIP_KLAUNCH(kk, dim3(grid), dim3(BLOCK), lds, st, W, np, direct ? A : (const T*)W, np, nT, ntasks, done, Dinv, failflag, abortflag, pthip::ctx().status_dev, trace);
-  if ((r = pthip::post_launch("chol_dag"))) return fail(r);
+  if ((r = pthip::post_launch("chol_dag"))) return r;
   if (trace) {  // profiling hook only: synchronises
     std::vector<long long> h((size_t)ntasks * 16);
     if (hipStreamSynchronize(st) == hipSuccess &&
@@ -1315,7 +1305,6 @@ int chol_dag(int lower, long long n, const T* A, T* L) {
     PTHIP_KLAUNCH((chol_finish_kernel<T>), dim3(nt, nt), dim3(BLOCK), 0, st, L, (const T*)W, (int)n, lower, (const int*)failflag, (int)np);
     r = pthip::post_launch("chol_finish");
   }
-  pthip_free(scratch);  // stream-ordered reuse keeps this safe
   return r;
 }
 
@@ -1324,18 +1313,18 @@ int chol_blocked(int lower, long long n, const T* A, T* L) {
   static const bool steps = getenv("PTHIP_CHOL") && !strcmp(getenv("PTHIP_CHOL"), "steps");
   if (!steps && !pthip::ctx().safe_mode) return chol_dag<T>(lower, n, A, L);
   hipStream_t st = pthip::ctx().stream;
+  pthip::Scratch mem;
   void* scratch = nullptr;
   const size_t wbytes = (size_t)n * n * sizeof(T);
-  int r = pthip_alloc(wbytes + 256, &scratch);
+  int r = mem.alloc(wbytes + 256, &scratch);
   if (r) return r;
   T* W = (T*)scratch;
   int* flag = (int*)((char*)scratch + wbytes);
   const int dt = sizeof(T) == 8 ? PTHIP_F64 : PTHIP_F32;
   const unsigned nt = (unsigned)((n + 31) / 32);
-  auto fail = [&](int rc) { pthip_free(scratch); return rc; };
-  if (hipError_t e = pthip::memset_async(flag, 0, 256, st); e != hipSuccess) return fail(pthip::check(e, "chol flag memset"));
+  if (hipError_t e = pthip::memset_async(flag, 0, 256, st); e != hipSuccess) return pthip::check(e, "chol flag memset");
   PTHIP_KLAUNCH((chol_stage_kernel<T>), dim3(nt, nt), dim3(BLOCK), 0, st, W, A, (int)n, lower, (int)n);
-  if ((r = pthip::post_launch("chol_stage"))) return fail(r);
+  if ((r = pthip::post_launch("chol_stage"))) return r;
   auto kd = potrf_lds_kernel<T>;
   auto kt = chol_trsm_kernel<T>;
   const size_t lds_d = (size_t)NBK * (NBK | 1) * sizeof(T);
@@ -1343,18 +1332,8 @@ int chol_blocked(int lower, long long n, const T* A, T* L) {
   auto km = chol_trsm_mfma_kernel<T>;
   const size_t lds_m = (size_t)(NBK * (NBK + 1) + CM_ROWS * (NBK + 1) + 4 * 16 * 17) * sizeof(T);
   static const bool use_mfma = !(getenv("PTHIP_CHOL_TRSM") && !strcmp(getenv("PTHIP_CHOL_TRSM"), "scalar"));
-  static bool attr_m = false;
-  if (!attr_m && lds_m > 64 * 1024) {
-    if (hipError_t e = hipFuncSetAttribute((const void*)km, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_m); e != hipSuccess)
-      return fail(pthip::check(e, "chol_trsm_mfma attribute"));
-    attr_m = true;
-  }
-  static bool attr_t = false;
-  if (!attr_t && lds_t > 64 * 1024) {
-    if (hipError_t e = hipFuncSetAttribute((const void*)kt, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_t); e != hipSuccess)
-      return fail(pthip::check(e, "chol_trsm attribute"));
-    attr_t = true;
-  }
+  if ((r = pthip::lds_opt_in((const void*)km, lds_m))) return r;
+  if ((r = pthip::lds_opt_in((const void*)kt, lds_t))) return r;
   // Two levels: NBO-column outer panels.  Inside one, every NBK-column step updates only the rest of
   // the outer panel (a tall m x <=NBO strip, K = NBK); the matrix to the right of the outer panel is
   // updated ONCE per outer panel with K = NBO — the GEMM runs at its large-K rate and the trailing
@@ -1366,7 +1345,7 @@ int chol_blocked(int lower, long long n, const T* A, T* L) {
       const int nb = (int)((Kend - k) < NBK ? (Kend - k) : NBK);
       T* D = W + k * n + k;
       PTHIP_KLAUNCH(kd, dim3(1), dim3(BLOCK), lds_d, st, D, (const T*)D, nb, 1, (const T*)nullptr, (T*)nullptr, (long long)n, flag);
-      if ((r = pthip::post_launch("chol diag"))) return fail(r);
+      if ((r = pthip::post_launch("chol diag"))) return r;
       const long long m = n - k - nb;
       if (m <= 0) break;
       if (nb == NBK && use_mfma) {
@@ -1374,12 +1353,12 @@ int chol_blocked(int lower, long long n, const T* A, T* L) {
       } else {
         PTHIP_KLAUNCH(kt, dim3((unsigned)((m + CT_ROWS - 1) / CT_ROWS)), dim3(CT_ROWS), lds_t, st, W, n, (int)k, nb, (int)n);
       }
-      if ((r = pthip::post_launch("chol trsm"))) return fail(r);
+      if ((r = pthip::post_launch("chol trsm"))) return r;
       const long long ncol = Kend - (k + nb);  // columns of the outer panel still to come
       if (ncol > 0) {
         const T* P = W + (k + nb) * n + k;  // the panel just solved: m x nb, row stride n
         r = pthip::gemm_inplace(dt, m, ncol, nb, -1.0, P, n, 1, P, 1, n, 1.0, W + (k + nb) * n + (k + nb), n);
-        if (r) return fail(r);
+        if (r) return r;
       }
     }
     const long long mo = n - Kend;
@@ -1393,13 +1372,11 @@ int chol_blocked(int lower, long long n, const T* A, T* L) {
       const long long wN = (mo - c0) < cw ? (mo - c0) : cw;
       r = pthip::gemm_inplace(dt, mo - c0, wN, wo, -1.0, Lp + c0 * n, n, 1, Lp + c0 * n, 1, n, 1.0,
                               W + (Kend + c0) * n + (Kend + c0), n);
-      if (r) return fail(r);
+      if (r) return r;
     }
   }
   PTHIP_KLAUNCH((chol_finish_kernel<T>), dim3(nt, nt), dim3(BLOCK), 0, st, L, (const T*)W, (int)n, lower, (const int*)flag, (int)n);
-  r = pthip::post_launch("chol_finish");
-  pthip_free(scratch);  // stream-ordered reuse keeps this safe
-  return r;
+  return pthip::post_launch("chol_finish");
 }
 
 // ---------------------------------------------------------------------------------
@@ -1602,8 +1579,7 @@ int potrf_typed(int lower, long long batch, long long n, const void* A, void* L,
   const size_t need = (size_t)n * ld * sizeof(T);
   if (need <= 160 * 1024 - 2560) {  // (the kernel's static LDS: a 64-entry column per wave + flags)
     auto k = potrf_lds_kernel<T>;
-    if (need > 64 * 1024)
-      PTHIP_CHECK(hipFuncSetAttribute((const void*)k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)need));
+    if (int r = pthip::lds_opt_in((const void*)k, need)) return r;
     PTHIP_KLAUNCH(k, dim3((unsigned)batch), dim3(BLOCK), need, st, (T*)L, (const T*)A, (int)n, lower,
                        (const T*)rhs, (T*)xout, 0LL, (int*)nullptr);
     return pthip::post_launch("potrf_lds");
@@ -1869,34 +1845,25 @@ int trsv_dag(int lower, int unit, long long n, long long nrhs, const T* Tm, long
   const int nB = (int)((n + TV - 1) / TV);
   const int nchunk = (int)((nrhs + TV_NR - 1) / TV_NR);
   const size_t boxbytes = (size_t)nB * TV * TV_NR * 2 * sizeof(unsigned long long);
+  pthip::Scratch mem;
   void* scratch = nullptr;
   const size_t flagbytes = 256 + ((size_t)nchunk * sizeof(int) + 255) / 256 * 256;  // fail, abort; from word 64 on: one ticket per chunk
-  int r = pthip_alloc(boxbytes * nchunk + flagbytes, &scratch);
+  int r = mem.alloc(boxbytes * nchunk + flagbytes, &scratch);
   if (r) return r;
-  auto fail = [&](int rc) { pthip_free(scratch); return rc; };
   int* flags = (int*)((char*)scratch + boxbytes * nchunk);
   auto kk = trsv_dag_kernel<T>;
   const size_t lds = (size_t)(2 * TV * TVS + TV * TV_NR + 4 * TV * TV_NR) * sizeof(T);
   static int resident = 0;
-  if (!resident) {
-    if (lds > 64 * 1024)
-      if (hipError_t e = hipFuncSetAttribute((const void*)kk, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds); e != hipSuccess)
-        return fail(pthip::check(e, "trsv_dag attribute"));
-    int per_cu = 0, dev = 0, cus = 0;
-    if (hipError_t e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, (const void*)kk, BLOCK, lds); e != hipSuccess)
-      return fail(pthip::check(e, "trsv_dag occupancy"));
-    if (hipError_t e = hipGetDevice(&dev); e != hipSuccess) return fail(pthip::check(e, "trsv_dag device"));
-    if (hipError_t e = hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev); e != hipSuccess)
-      return fail(pthip::check(e, "trsv_dag device attribute"));
-    resident = per_cu * cus;
-  }
+  // (every workgroup the device holds counts here: no cap per CU; a kernel that fits no CU at all is an error,
+  //  not a reason to fall back)
+  if (!resident)
+    if ((r = pthip::resident_workgroups((const void*)kk, BLOCK, lds, INT_MAX, &resident))) return r;
   if (nB > resident) {
     // more row blocks than the device holds workgroups (a smaller part, or n beyond 64 x CUs x occupancy): the
     // persistent kernel would wait on blocks that are not running.  The blocked solve has no such requirement.
-    pthip_free(scratch);
     return 1 << 30;  // (the caller falls back to trsm_blocked)
   }
-  if (hipError_t e = pthip::memset_async(scratch, 0, boxbytes * nchunk + flagbytes, st); e != hipSuccess) return fail(pthip::check(e, "trsv box memset"));
+  if (hipError_t e = pthip::memset_async(scratch, 0, boxbytes * nchunk + flagbytes, st); e != hipSuccess) return pthip::check(e, "trsv box memset");
   // solve coordinates: p = lower ? i : n-1-i
   const long long sg = lower ? 1 : -1;
   const T* Tp = lower ? Tm : Tm + (n - 1) * (sT0 + sT1);
@@ -1907,12 +1874,10 @@ int trsv_dag(int lower, int unit, long long n, long long nrhs, const T* Tm, long
     PTHIP_KLAUNCH(kk, dim3((unsigned)nB), dim3(BLOCK), lds, st, Xp + (long long)c * TV_NR, sg * nrhs, Tp, sg * sT0, sg * sT1,
                   Bp + (long long)c * TV_NR, sg * nrhs, (int)n, nr, unit,
                   (unsigned long long*)((char*)scratch + boxbytes * c), flags, flags + 1, flags + 64 + c, pthip::ctx().status_dev);
-    if ((r = pthip::post_launch("trsv_dag"))) return fail(r);
+    if ((r = pthip::post_launch("trsv_dag"))) return r;
   }
   PTHIP_KLAUNCH((nan_fill_if_kernel<T>), dim3(256), dim3(BLOCK), 0, st, out, n * nrhs, (const int*)flags);
-  r = pthip::post_launch("trsm nan fill");
-  pthip_free(scratch);
-  return r;
+  return pthip::post_launch("trsm nan fill");
 }
 
 // Inverses of all 256 x 256 diagonal blocks of T in one launch (block b -> Tinv[b], dense 256 x 256
@@ -2143,29 +2108,23 @@ int trsm_blocked(int lower, int unit, long long n, long long nrhs, const T* Tm, 
   const long long IB = base64 ? TV : TB;  // rows of the blocks inverted inside a workgroup
   const long long nB = (n + IB - 1) / IB;
   const size_t invbytes = (size_t)nB * IB * IB * sizeof(T), tmpbytes = (size_t)4 * TB * nrhs * sizeof(T);  // (steps of up to 1024 rows)
+  pthip::Scratch mem;  // the block inverses and the step scratch, then one block per doubling level
   void* scratch = nullptr;
-  int r = pthip_alloc(invbytes + tmpbytes + 256, &scratch);
+  int r = mem.alloc(invbytes + tmpbytes + 256, &scratch);
   if (r) return r;
-  auto fail = [&](int rc) { pthip_free(scratch); return rc; };
   T* Tinv = (T*)scratch;
   T* Xt = (T*)((char*)scratch + invbytes);
   int* flag = (int*)((char*)scratch + invbytes + tmpbytes);
-  if (hipError_t e = pthip::memset_async(Xt, 0, tmpbytes + 256, st); e != hipSuccess) return fail(pthip::check(e, "trsm scratch memset"));
+  if (hipError_t e = pthip::memset_async(Xt, 0, tmpbytes + 256, st); e != hipSuccess) return pthip::check(e, "trsm scratch memset");
   if (hipError_t e = pthip::memcpy_async(out, B, (size_t)n * nrhs * sizeof(T), hipMemcpyDeviceToDevice, st); e != hipSuccess)
-    return fail(pthip::check(e, "trsm rhs copy"));
+    return pthip::check(e, "trsm rhs copy");
   auto ki = tri_inv256_kernel<T>;
   const size_t lds = (size_t)(2 * TV * TVS + 4 * 16 * 17) * sizeof(T);
-  static bool attr = false;
-  if (!attr && lds > 64 * 1024) {
-    if (hipError_t e = hipFuncSetAttribute((const void*)ki, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds); e != hipSuccess)
-      return fail(pthip::check(e, "tri_inv256 attribute"));
-    if (hipError_t e = hipFuncSetAttribute((const void*)tri_inv64_kernel<T>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds); e != hipSuccess)
-      return fail(pthip::check(e, "tri_inv64 attribute"));
-    attr = true;
-  }
+  if ((r = pthip::lds_opt_in((const void*)ki, lds))) return r;
+  if ((r = pthip::lds_opt_in((const void*)tri_inv64_kernel<T>, lds))) return r;
   if (base64) PTHIP_KLAUNCH((tri_inv64_kernel<T>), dim3((unsigned)nB), dim3(BLOCK), lds, st, Tinv, Tm, sT0, sT1, (int)n, lower, unit, flag);
   else PTHIP_KLAUNCH(ki, dim3((unsigned)nB), dim3(BLOCK), lds, st, Tinv, Tm, sT0, sT1, (int)n, lower, unit, flag);
-  if ((r = pthip::post_launch(base64 ? "tri_inv64" : "tri_inv256"))) return fail(r);
+  if ((r = pthip::post_launch(base64 ? "tri_inv64" : "tri_inv256"))) return r;
   // Round 4: with many right-hand sides the 256-row steps are 25 dependent launches at n = 2048 whose solve GEMMs
   // (M = 256) fill an eighth of the chip.  The block inverses are doubled once (256 -> 512: per pair
   // inv = [[A^-1, 0], [-D^-1 C A^-1, D^-1]], two batched GEMMs and an assemble launch for all pairs), then the same
@@ -2173,18 +2132,15 @@ int trsm_blocked(int lower, int unit, long long n, long long nrhs, const T* Tm, 
   // inverse is applied: PTHIP_TRSM_BLOCK=256 keeps the round-3 form, 1024 doubles twice.)
   long long SB = IB;  // rows per step
   T* InvCur = Tinv;
-  void* lvl_scratch[4] = {nullptr, nullptr, nullptr, nullptr};
-  auto fail2 = [&](int rc) { for (void* q : lvl_scratch) if (q) pthip_free(q); return fail(rc); };
   for (int lvl = 0; lvl < 4 && SB * 2 <= blk_env && nrhs >= 2 * SB && n > SB; lvl++) {
     const long long sblk = SB, nb_s = (n + sblk - 1) / sblk, npairs = (nb_s + 1) / 2;
     const size_t inv2bytes = (size_t)npairs * 4 * sblk * sblk * sizeof(T), offbytes = (size_t)npairs * sblk * sblk * sizeof(T);
     void* q = nullptr;
-    if ((r = pthip_alloc(inv2bytes + 2 * offbytes + 256, &q))) return fail2(r);
-    lvl_scratch[lvl] = q;
+    if ((r = mem.alloc(inv2bytes + 2 * offbytes + 256, &q))) return r;
     T* Inv2 = (T*)q;
     T* tmp = (T*)((char*)q + inv2bytes);
     T* off = (T*)((char*)q + inv2bytes + offbytes);
-    if (hipError_t e = pthip::memset_async(tmp, 0, 2 * offbytes, st); e != hipSuccess) return fail2(pthip::check(e, "trsm level memset"));
+    if (hipError_t e = pthip::memset_async(tmp, 0, 2 * offbytes, st); e != hipSuccess) return pthip::check(e, "trsm level memset");
     long long full = 0;  // pairs whose second block is complete
     while (full < npairs && (2 * full + 2) * sblk <= n) full++;
     const long long with_b1 = nb_s / 2;  // pairs that have a second block at all (complete or partial)
@@ -2194,30 +2150,30 @@ int trsm_blocked(int lower, int unit, long long n, long long nrhs, const T* Tm, 
     if (lower) {
       // tmp = C A^-1 (valid rows only), off = -D^-1 tmp
       if (full > 0)
-        if ((r = pthip_gemm(dt, full, sblk, sblk, sblk, 1.0, C0, pstride, sT0, sT1, InvCur, 2 * sblk * sblk, sblk, 1, 0.0, nullptr, 0, 0, 0, tmp))) return fail2(r);
+        if ((r = pthip_gemm(dt, full, sblk, sblk, sblk, 1.0, C0, pstride, sT0, sT1, InvCur, 2 * sblk * sblk, sblk, 1, 0.0, nullptr, 0, 0, 0, tmp))) return r;
       if (with_b1 > full) {
         const long long pidx = full, rows = n - (2 * pidx + 1) * sblk;
         if ((r = pthip::gemm_inplace(dt, rows, sblk, sblk, 1.0, C0 + pidx * pstride, sT0, sT1, InvCur + 2 * pidx * sblk * sblk, sblk, 1, 0.0,
-                                     tmp + pidx * sblk * sblk, sblk))) return fail2(r);
+                                     tmp + pidx * sblk * sblk, sblk))) return r;
       }
       if (with_b1 > 0)
         if ((r = pthip_gemm(dt, with_b1, sblk, sblk, sblk, -1.0, InvCur + sblk * sblk, 2 * sblk * sblk, sblk, 1, tmp, sblk * sblk, sblk, 1, 0.0, nullptr, 0, 0,
-                            0, off))) return fail2(r);
+                            0, off))) return r;
     } else {
       // tmp = A^-1 C (valid columns only), off = -tmp D^-1
       if (full > 0)
-        if ((r = pthip_gemm(dt, full, sblk, sblk, sblk, 1.0, InvCur, 2 * sblk * sblk, sblk, 1, C0, pstride, sT0, sT1, 0.0, nullptr, 0, 0, 0, tmp))) return fail2(r);
+        if ((r = pthip_gemm(dt, full, sblk, sblk, sblk, 1.0, InvCur, 2 * sblk * sblk, sblk, 1, C0, pstride, sT0, sT1, 0.0, nullptr, 0, 0, 0, tmp))) return r;
       if (with_b1 > full) {
         const long long pidx = full, cols = n - (2 * pidx + 1) * sblk;
         if ((r = pthip::gemm_inplace(dt, sblk, cols, sblk, 1.0, InvCur + 2 * pidx * sblk * sblk, sblk, 1, C0 + pidx * pstride, sT0, sT1, 0.0,
-                                     tmp + pidx * sblk * sblk, sblk))) return fail2(r);
+                                     tmp + pidx * sblk * sblk, sblk))) return r;
       }
       if (with_b1 > 0)
         if ((r = pthip_gemm(dt, with_b1, sblk, sblk, sblk, -1.0, tmp, sblk * sblk, sblk, 1, InvCur + sblk * sblk, 2 * sblk * sblk, sblk, 1, 0.0, nullptr, 0, 0,
-                            0, off))) return fail2(r);
+                            0, off))) return r;
     }
     PTHIP_KLAUNCH((tri_inv_assemble_kernel<T>), dim3(64, (unsigned)npairs), dim3(BLOCK), 0, st, Inv2, (const T*)InvCur, (const T*)off, (int)sblk, (int)nb_s, lower);
-    if ((r = pthip::post_launch("tri_inv_assemble"))) return fail2(r);
+    if ((r = pthip::post_launch("tri_inv_assemble"))) return r;
     InvCur = Inv2;
     SB = 2 * sblk;
   }
@@ -2234,19 +2190,16 @@ int trsm_blocked(int lower, int unit, long long n, long long nrhs, const T* Tm, 
   if (lower) {
     for (long long k0 = 0; k0 < n; k0 += SB) {
       const long long nb = (n - k0) < SB ? (n - k0) : SB;
-      if ((r = step(k0, nb, k0 + nb, n))) return fail2(r);
+      if ((r = step(k0, nb, k0 + nb, n))) return r;
     }
   } else {
     for (long long k0 = (n - 1) / SB * SB; k0 >= 0; k0 -= SB) {
       const long long nb = (n - k0) < SB ? (n - k0) : SB;
-      if ((r = step(k0, nb, 0, k0))) return fail2(r);
+      if ((r = step(k0, nb, 0, k0))) return r;
     }
   }
   PTHIP_KLAUNCH((nan_fill_if_kernel<T>), dim3(256), dim3(BLOCK), 0, st, out, n * nrhs, (const int*)flag);
-  r = pthip::post_launch("trsm nan fill");
-  for (void* q : lvl_scratch) if (q) pthip_free(q);
-  pthip_free(scratch);
-  return r;
+  return pthip::post_launch("trsm nan fill");
 }
 
 template <class T>
@@ -2262,8 +2215,7 @@ int trsm_typed(int lower, int unit, long long batch, long long n, long long nrhs
 #define LAUNCH_TRSV(RPL)                                                                         \
   do {                                                                                           \
     auto k = trsv_lds_kernel<T, RPL>;                                                            \
-    if (need > 64 * 1024)                                                                        \
-      PTHIP_CHECK(hipFuncSetAttribute((const void*)k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)need)); \
+    if (int r = pthip::lds_opt_in((const void*)k, need)) return r;                               \
     PTHIP_KLAUNCH(k, dim3((unsigned)batch), dim3(BLOCK), need, st, (T*)out, (const T*)Tm,   \
                        sTb, sT0, sT1, (const T*)B, sBb, (int)n, lower, unit);                    \
   } while (0)
@@ -2286,8 +2238,7 @@ int trsm_typed(int lower, int unit, long long batch, long long n, long long nrhs
 #define LAUNCH_FEW(RPL)                                                                                                            \
   do {                                                                                                                             \
     auto k = trsm_few_lds_kernel<T, RPL>;                                                                                          \
-    if (need_few > 64 * 1024)                                                                                                      \
-      PTHIP_CHECK(hipFuncSetAttribute((const void*)k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)need_few));                 \
+    if (int r = pthip::lds_opt_in((const void*)k, need_few)) return r;                                                             \
     PTHIP_KLAUNCH(k, dim3((unsigned)batch), dim3(BLOCK), need_few, st, (T*)out, (const T*)Tm, sTb, sT0, sT1, (const T*)B, sBb,     \
                   (int)n, (int)nrhs, lower, unit);                                                                                 \
   } while (0)
@@ -2299,8 +2250,7 @@ int trsm_typed(int lower, int unit, long long batch, long long n, long long nrhs
     }
     if (need <= 160 * 1024 - 256 && (lds_always || n <= TV || nrhs < 64 || batch > 2)) {
       auto k = trsm_lds_kernel<T>;
-      if (need > 64 * 1024)
-        PTHIP_CHECK(hipFuncSetAttribute((const void*)k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)need));
+      if (int r = pthip::lds_opt_in((const void*)k, need)) return r;
       PTHIP_KLAUNCH(k, dim3((unsigned)((nrhs + BLOCK - 1) / BLOCK), (unsigned)batch), dim3(BLOCK), need,
                          st, (T*)out, (const T*)Tm, sTb, sT0, sT1, (const T*)B, sBb, (int)n, (int)nrhs, lower, unit, (int*)nullptr);
       return pthip::post_launch("trsm_lds");

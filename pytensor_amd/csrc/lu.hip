@@ -284,15 +284,14 @@ __global__ __launch_bounds__(BLOCK) void getrf_reg_kernel(T* __restrict__ LUout,
 template <class T, int NB>
 int launch_getrf_reg(long long batch, long long n, const void* A, void* LU, void* perm, void* sign, void* logabs,
                      int flag_singular) {
+  pthip::Scratch mem;
   void* stage = nullptr;  // multipliers in physical row order until the permutation is known
-  int r = pthip_alloc((size_t)batch * n * n * sizeof(T), &stage);
+  int r = mem.alloc((size_t)batch * n * n * sizeof(T), &stage);
   if (r) return r;
   PTHIP_KLAUNCH((getrf_reg_kernel<T, NB>), dim3((unsigned)batch), dim3(BLOCK), 0, pthip::ctx().stream, (T*)LU,
                      (const T*)A, (long long*)perm, (T*)sign, (T*)logabs, (int)n, (T*)stage,
                      flag_singular ? (int*)pthip_status_ptr() : (int*)nullptr);
-  r = pthip::post_launch("getrf_reg");
-  pthip_free(stage);  // stream-ordered reuse keeps this safe
-  return r;
+  return pthip::post_launch("getrf_reg");
 }
 
 
@@ -573,51 +572,45 @@ int getrf_blocked(long long n, const T* A, T* LU, long long* perm, T* sign, T* l
   const int nWmax = (int)((n + BLOCK - 1) / BLOCK);
   const size_t boxbytes = (size_t)LB * nWmax * (LB + 2) * 16, boxkbytes = (size_t)LB * LB * 16;
   const size_t ibytes = ((size_t)n * sizeof(int) + 255) / 256 * 256;
+  pthip::Scratch mem;
   void* scratch = nullptr;
-  int r = pthip_alloc(boxbytes + boxkbytes + ibytes + 256, &scratch);
+  int r = mem.alloc(boxbytes + boxkbytes + ibytes + 256, &scratch);
   if (r) return r;
-  auto fail = [&](int rc) { pthip_free(scratch); return rc; };
   unsigned long long* box = (unsigned long long*)scratch;
   unsigned long long* boxk = (unsigned long long*)((char*)scratch + boxbytes);
   int* ipiv = (int*)((char*)scratch + boxbytes + boxkbytes);
   int* flags = (int*)((char*)scratch + boxbytes + boxkbytes + ibytes);  // [0] info, [1] abort
-  if (hipError_t e = pthip::memset_async(flags, 0, 256, st); e != hipSuccess) return fail(pthip::check(e, "lu flags memset"));
+  if (hipError_t e = pthip::memset_async(flags, 0, 256, st); e != hipSuccess) return pthip::check(e, "lu flags memset");
   if (hipError_t e = pthip::memcpy_async(LU, A, (size_t)n * n * sizeof(T), hipMemcpyDeviceToDevice, st); e != hipSuccess)
-    return fail(pthip::check(e, "lu copy"));
+    return pthip::check(e, "lu copy");
   for (long long k0 = 0; k0 < n; k0 += LB) {
     const int pw = (int)((n - k0) < LB ? (n - k0) : LB);
     const int nW = (int)((n - k0 + BLOCK - 1) / BLOCK);
     if (nW > 1)
-      if (hipError_t e = pthip::memset_async(box, 0, boxbytes + boxkbytes, st); e != hipSuccess) return fail(pthip::check(e, "lu box memset"));
+      if (hipError_t e = pthip::memset_async(box, 0, boxbytes + boxkbytes, st); e != hipSuccess) return pthip::check(e, "lu box memset");
     PTHIP_KLAUNCH((lu_panel_kernel<T>), dim3((unsigned)nW), dim3(BLOCK), 0, st, LU, n, (int)n, (int)k0, nW, box, boxk, ipiv, flags, flags + 1,
                   pthip::ctx().status_dev);
-    if ((r = pthip::post_launch("lu_panel"))) return fail(r);
+    if ((r = pthip::post_launch("lu_panel"))) return r;
     if (n - pw > 0) {
       PTHIP_KLAUNCH((lu_laswp_kernel<T>), dim3((unsigned)((n - pw + BLOCK - 1) / BLOCK)), dim3(BLOCK), 0, st, LU, n, (int)n, (int)k0, pw, (const int*)ipiv);
-      if ((r = pthip::post_launch("lu_laswp"))) return fail(r);
+      if ((r = pthip::post_launch("lu_laswp"))) return r;
     }
     const long long rest = n - k0 - pw;
     if (rest > 0) {
       PTHIP_KLAUNCH((lu_u12_kernel<T>), dim3((unsigned)((rest + BLOCK - 1) / BLOCK)), dim3(BLOCK), 0, st, LU, n, (int)n, (int)k0, pw);
-      if ((r = pthip::post_launch("lu_u12"))) return fail(r);
+      if ((r = pthip::post_launch("lu_u12"))) return r;
       r = pthip::gemm_inplace(dt, rest, rest, pw, -1.0, LU + (k0 + pw) * n + k0, n, 1, LU + k0 * n + k0 + pw, n, 1, 1.0,
                               LU + (k0 + pw) * n + k0 + pw, n);
-      if (r) return fail(r);
+      if (r) return r;
     }
   }
   auto kf = lu_finish_kernel<T>;
   const size_t sh = (size_t)n * sizeof(int);
-  static bool attr = false;
-  if (!attr && sh > 48 * 1024) {
-    if (hipError_t e = hipFuncSetAttribute((const void*)kf, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024 - 4096); e != hipSuccess)
-      return fail(pthip::check(e, "lu_finish attribute"));
-    attr = true;
-  }
+  if (sh > 48 * 1024)
+    if ((r = pthip::lds_opt_in((const void*)kf, 160 * 1024 - 4096))) return r;
   PTHIP_KLAUNCH(kf, dim3(1), dim3(BLOCK), sh, st, (const T*)LU, n, (int)n, (const int*)ipiv, (const int*)flags, perm, sign, logabs,
                 flag_singular ? pthip::ctx().status_dev : (int*)nullptr);
-  r = pthip::post_launch("lu_finish");
-  pthip_free(scratch);
-  return r;
+  return pthip::post_launch("lu_finish");
 }
 
 
@@ -1023,10 +1016,10 @@ int getrf_blocked2(long long n, const T* A, T* LU, long long* perm, T* sign, T* 
   const size_t boxbytes = (size_t)PB * nWmax * (PB + 2) * 16, boxkbytes = 0;
   const size_t ibytes = ((size_t)n * sizeof(int) + 255) / 256 * 256;
   const size_t pbytes = ((size_t)2 * (1 + 3 * PB) * sizeof(int) + 255) / 256 * 256;  // two panels' lists (look-ahead)
+  pthip::Scratch mem;
   void* scratch = nullptr;
-  int r = pthip_alloc(boxbytes + boxkbytes + ibytes + pbytes + 256, &scratch);
+  int r = mem.alloc(boxbytes + boxkbytes + ibytes + pbytes + 256, &scratch);
   if (r) return r;
-  auto fail = [&](int rc) { pthip_free(scratch); return rc; };
   unsigned long long* box = (unsigned long long*)scratch;
   int* ipiv = (int*)((char*)scratch + boxbytes + boxkbytes);
   int* plist = (int*)((char*)scratch + boxbytes + boxkbytes + ibytes);
@@ -1037,17 +1030,12 @@ int getrf_blocked2(long long n, const T* A, T* LU, long long* perm, T* sign, T* 
   const unsigned long long nonce = (++calls) * 0xD1B54A32D192ED03ull;
   // (one fill for the whole call: the pair tags carry the column index, a stale pair of an earlier panel never validates)
   if (hipError_t e = pthip::memset_async(scratch, 0, boxbytes + boxkbytes + ibytes + pbytes + 256, st); e != hipSuccess)
-    return fail(pthip::check(e, "lu scratch memset"));
+    return pthip::check(e, "lu scratch memset");
   if (hipError_t e = pthip::memcpy_async(LU, A, (size_t)n * n * sizeof(T), hipMemcpyDeviceToDevice, st); e != hipSuccess)
-    return fail(pthip::check(e, "lu copy"));
+    return pthip::check(e, "lu copy");
   auto ks = lu_swap_u12_kernel<T, PB, CB>;
   const size_t sh = ((size_t)PB * CB + (size_t)PB * (PB + 1)) * sizeof(T);
-  static bool attr = false;
-  if (!attr && sh > 48 * 1024) {
-    if (hipError_t e = hipFuncSetAttribute((const void*)ks, hipFuncAttributeMaxDynamicSharedMemorySize, (int)sh); e != hipSuccess)
-      return fail(pthip::check(e, "lu_swap_u12 attribute"));
-    attr = true;
-  }
+  if ((r = pthip::lds_opt_in((const void*)ks, sh))) return r;
   // Look-ahead (round 4): the trailing update of panel k — interchanges + U12 of every column outside the NEXT panel,
   // and their GEMM — runs on a second stream while the next panel is being factored; only the next panel's own
   // columns are swapped / solved / updated on the panel stream first.  (panel 125 us, swap 26, GEMM 30 per 32 columns
@@ -1107,36 +1095,32 @@ int getrf_blocked2(long long n, const T* A, T* LU, long long* perm, T* sign, T* 
       else LU_PANEL2_LAUNCH(false, false, BLOCK);
     }
 #undef LU_PANEL2_LAUNCH
-    if ((r = pthip::post_launch("lu_panel2"))) return fail(r);
+    if ((r = pthip::post_launch("lu_panel2"))) return r;
     const long long right0 = k0 + pw, nright = n - right0;
     if (!lookahead) {
-      if ((r = launch_swap(pl, k0, pw, 0, k0, right0, nright))) return fail(r);
-      if ((r = launch_gemm(k0, pw, right0, nright))) return fail(r);
+      if ((r = launch_swap(pl, k0, pw, 0, k0, right0, nright))) return r;
+      if ((r = launch_gemm(k0, pw, right0, nright))) return r;
       continue;
     }
     // the next panel's columns on this stream; everything else on the side stream, behind the panel
     const long long nnext = nright < PB ? nright : PB;
     if (panel_index > 0)
-      if ((r = pthip_stream_wait(cur, side))) return fail(r);  // the previous trailing update touched these columns
-    if ((r = launch_swap(pl, k0, pw, right0, nnext, 0, 0))) return fail(r);
-    if ((r = launch_gemm(k0, pw, right0, nnext))) return fail(r);
-    if ((r = pthip_stream_wait(side, cur))) return fail(r);  // (behind this panel; the two small launches above ride along)
-    if ((r = on_stream(side))) return fail(r);
+      if ((r = pthip_stream_wait(cur, side))) return r;  // the previous trailing update touched these columns
+    if ((r = launch_swap(pl, k0, pw, right0, nnext, 0, 0))) return r;
+    if ((r = launch_gemm(k0, pw, right0, nnext))) return r;
+    if ((r = pthip_stream_wait(side, cur))) return r;  // (behind this panel; the two small launches above ride along)
+    if ((r = on_stream(side))) return r;
     r = launch_swap(pl, k0, pw, 0, k0, right0 + nnext, nright - nnext);
     if (!r) r = launch_gemm(k0, pw, right0 + nnext, nright - nnext);
     const int r2 = on_stream(cur);
-    if (r || r2) return fail(r ? r : r2);
+    if (r || r2) return r ? r : r2;
   }
   if (lookahead)
-    if ((r = pthip_stream_wait(cur, side))) return fail(r);
+    if ((r = pthip_stream_wait(cur, side))) return r;
   auto kf = lu_finish_kernel<T>;
   const size_t shf = (size_t)n * sizeof(int);
-  static bool attrf = false;
-  if (!attrf && shf > 48 * 1024) {
-    if (hipError_t e = hipFuncSetAttribute((const void*)kf, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024 - 4096); e != hipSuccess)
-      return fail(pthip::check(e, "lu_finish attribute"));
-    attrf = true;
-  }
+  if (shf > 48 * 1024)
+    if ((r = pthip::lds_opt_in((const void*)kf, 160 * 1024 - 4096))) return r;
   PTHIP_KLAUNCH(kf, dim3(1), dim3(BLOCK), shf, st, (const T*)LU, n, (int)n, (const int*)ipiv, (const int*)flags, perm, sign, logabs,
                 flag_singular ? pthip::ctx().status_dev : (int*)nullptr);
   r = pthip::post_launch("lu_finish");
@@ -1146,7 +1130,6 @@ int getrf_blocked2(long long n, const T* A, T* LU, long long* perm, T* sign, T* 
       fprintf(stderr, "[pthip lu prof] n=%lld PB=%d f%d: per column us  A %.2f  B %.2f  C %.2f  rotate %.2f | loop %.2f us/col, shader clock %.0f MHz\n", n, PB,
               (int)sizeof(T) * 8, h[0] * 0.01 / n, h[1] * 0.01 / n, h[2] * 0.01 / n, h[3] * 0.01 / n, h[5] * 0.01 / n, h[5] ? (double)h[4] / (h[5] * 0.01) : 0.0);
   }
-  pthip_free(scratch);
   return r;
 }
 
@@ -1168,20 +1151,17 @@ int getrf_typed(long long batch, long long n, const void* A, void* LU, void* per
   if (need <= 160 * 1024 - 8192 || (unblocked && n <= 512) || pthip::ctx().safe_mode) {
     const bool lds = need <= 160 * 1024 - 8192;
     auto k = getrf_kernel<T>;
+    pthip::Scratch mem;
     void* scratch = nullptr;
     if (lds) {
-      if (need > 48 * 1024)
-        PTHIP_CHECK(hipFuncSetAttribute((const void*)k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)need));
+      if (int r = pthip::lds_opt_in((const void*)k, need)) return r;
     } else {
-      int r = pthip_alloc((size_t)batch * n * n * sizeof(T), &scratch);
-      if (r) return r;
+      if (int r = mem.alloc((size_t)batch * n * n * sizeof(T), &scratch)) return r;
     }
     PTHIP_KLAUNCH(k, dim3((unsigned)batch), dim3(BLOCK), lds ? need : 0, st, (T*)LU, (const T*)A,
                        (long long*)perm, (T*)sign, (T*)logabs, (int)n, lds ? 1 : 0, (T*)scratch,
                        flag_singular ? (int*)pthip_status_ptr() : (int*)nullptr);
-    int r = pthip::post_launch("getrf");
-    if (scratch) pthip_free(scratch);  // stream-ordered reuse keeps this safe
-    return r;
+    return pthip::post_launch("getrf");
   }
   // beyond one CU's LDS: the blocked factorisation, one matrix after the other
   // (PTHIP_LU_PANEL: "v1" = the round-3 unrolled 32-column panel, "32" / "64" = the looped panel of that width)

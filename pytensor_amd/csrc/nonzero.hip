@@ -66,13 +66,12 @@ extern "C" int pthip_nonzero(int64_t n, const void* mask, void* idx_out, void* c
     return 0;
   }
   const long long nb = (n + TILE - 1) / TILE;
+  pthip::Scratch mem;
   void* counts = nullptr;
-  int r = pthip_alloc((size_t)nb * sizeof(long long), &counts);
+  int r = mem.alloc((size_t)nb * sizeof(long long), &counts);
   if (r) return r;
   PTHIP_KLAUNCH(nz_count_kernel, dim3((unsigned)nb), dim3(BLOCK), 0, st, (const unsigned char*)mask, (long long)n, (long long*)counts);
   PTHIP_KLAUNCH(nz_scan_kernel, dim3(1), dim3(BLOCK), 0, st, (long long*)counts, nb, (long long*)count_out);
   PTHIP_KLAUNCH(nz_write_kernel, dim3((unsigned)nb), dim3(BLOCK), 0, st, (const unsigned char*)mask, (long long)n, (const long long*)counts, (long long*)idx_out);
-  r = pthip::post_launch("nonzero");
-  pthip_free(counts);  // stream-ordered reuse keeps this safe
-  return r;
+  return pthip::post_launch("nonzero");
 }

@@ -320,11 +320,7 @@ int dare_typed(long long batch, long long m, long long n, const void* A, const v
   if (!in_lds && ws_bytes < (size_t)batch * lds)
     return pthip::set_error("pthip_dare: workspace of %zu bytes, %zu needed", ws_bytes, (size_t)batch * lds);
   auto k = dare_sda_kernel<T, TO>;
-  static bool attr = false;
-  if (!attr) {
-    PTHIP_CHECK(hipFuncSetAttribute((const void*)k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kDareLdsBudget));
-    attr = true;
-  }
+  if (int r = pthip::lds_opt_in((const void*)k, kDareLdsBudget)) return r;
   hipStream_t st = pthip::ctx().stream;
   PTHIP_KLAUNCH(k, dim3((unsigned)batch), dim3(DARE_BLOCK), in_lds ? lds : 0, st, (const T*)A, (const T*)B, (const T*)Q,
                 (const T*)R, (TO*)X, (int*)steps, (int)m, (int)n, in_lds ? 1 : 0, (double*)ws);

@@ -865,11 +865,9 @@ int lse_rows_typed(long long rows, long long cols, const void* x, void* out) {
     // kernel (39.4 -> 33.6 us at 1e6 x 10, reads AND writes staged) loses 15 % in this read-only one (25.3 -> 29.4 us cold)
     static const int vec_env = [] { const char* e = getenv("PTHIP_LSE_SMALL_VEC"); return e ? atoi(e) : 0; }();
     const int vec = vec_env && ((uintptr_t)x % 16) == 0 && ((BLOCK * cols * sizeof(T)) % 16) == 0;
-    static bool lds_raised = false;  // (up to 256 x 33 x 8 = 67.6 KB: beyond the 64 KB a launch may ask for by default)
-    if (lds > 48 * 1024 && !lds_raised) {
-      PTHIP_CHECK(hipFuncSetAttribute((const void*)lse_rows_small_kernel<T, 32>, hipFuncAttributeMaxDynamicSharedMemorySize, 80 * 1024));
-      lds_raised = true;
-    }
+    // (up to 256 x 33 x 8 = 67.6 KB: beyond the 64 KB a launch may ask for by default)
+    if (lds > 48 * 1024)
+      if (int r = pthip::lds_opt_in((const void*)lse_rows_small_kernel<T, 32>, 80 * 1024)) return r;
     if (cols <= 8)
       PTHIP_KLAUNCH((lse_rows_small_kernel<T, 8>), dim3(grid), dim3(BLOCK), lds, st, (T*)out, (const T*)x, rows, (int)cols, magic, vec);
     else if (cols <= 16)

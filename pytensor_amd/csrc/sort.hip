@@ -139,11 +139,12 @@ int sort_typed(long long rows, long long n, const void* in, void* out_vals, void
                        (T*)out_vals, (long long*)out_idx);
     return pthip::post_launch("sort_lds");
   }
+  pthip::Scratch mem;
   void *keys = nullptr, *idx = nullptr;
-  int r = pthip_alloc((size_t)rows * P * sizeof(T), &keys);
+  int r = mem.alloc((size_t)rows * P * sizeof(T), &keys);
   if (r) return r;
-  r = pthip_alloc((size_t)rows * P * sizeof(int), &idx);
-  if (r) { pthip_free(keys); return r; }
+  r = mem.alloc((size_t)rows * P * sizeof(int), &idx);
+  if (r) return r;
   const unsigned tiles = (unsigned)(rows * (P / TILE));
   PTHIP_KLAUNCH(sort_init_kernel<T>, dim3(grid_for(rows * P)), dim3(BLOCK), 0, st, (const T*)in, rows, (int)n, P, (T*)keys, (int*)idx);
   PTHIP_KLAUNCH(sort_tile_kernel<T>, dim3(tiles), dim3(BLOCK), 0, st, (T*)keys, (int*)idx, (int)n, P, 0, 1);
@@ -153,10 +154,7 @@ int sort_typed(long long rows, long long n, const void* in, void* out_vals, void
     PTHIP_KLAUNCH(sort_tile_kernel<T>, dim3(tiles), dim3(BLOCK), 0, st, (T*)keys, (int*)idx, (int)n, P, (int)k, 0);
   }
   PTHIP_KLAUNCH(sort_store_kernel<T>, dim3(grid_for(rows * n)), dim3(BLOCK), 0, st, (const T*)keys, (const int*)idx, rows, (int)n, P, (T*)out_vals, (long long*)out_idx);
-  r = pthip::post_launch("sort");
-  pthip_free(keys);  // stream-ordered reuse keeps this safe
-  pthip_free(idx);
-  return r;
+  return pthip::post_launch("sort");
 }
 
 }  // namespace

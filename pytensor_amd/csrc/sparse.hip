@@ -252,15 +252,14 @@ int exclusive_scan_i32(const int* in, long long n, int* out, hipStream_t st) {
     return 0;
   }
   const long long nb = (n + SCAN_TILE - 1) / SCAN_TILE;
+  pthip::Scratch mem;
   void* sums = nullptr;
-  int r = pthip_alloc((size_t)(nb + 1) * sizeof(long long), &sums);
+  int r = mem.alloc((size_t)(nb + 1) * sizeof(long long), &sums);
   if (r) return r;
   PTHIP_KLAUNCH(scan_tiles_kernel, dim3((unsigned)nb), dim3(BLOCK), 0, st, in, n, (long long*)sums);
   PTHIP_KLAUNCH(scan_sums_kernel, dim3(1), dim3(BLOCK), 0, st, (long long*)sums, nb);
   PTHIP_KLAUNCH(scan_apply_kernel, dim3((unsigned)nb), dim3(BLOCK), 0, st, in, n, (const long long*)sums, nb, out);
-  r = pthip::post_launch("exclusive_scan");
-  pthip_free(sums);  // (stream-ordered pool)
-  return r;
+  return pthip::post_launch("exclusive_scan");
 }
 
 // ---- transpose: stable LSD radix sort of the entries by column ---------------------------------------
@@ -349,13 +348,14 @@ int transpose_t(long long rows, long long n, long long nnz, const void* data, co
     return 0;
   }
   const long long nb = (nnz + BLOCK - 1) / BLOCK;
+  pthip::Scratch mem;
   void *keys = nullptr, *vals = nullptr, *keys2 = nullptr, *vals2 = nullptr, *rowid = nullptr, *counts = nullptr, *hist = nullptr,
        *offs = nullptr;
   const size_t ib = (size_t)nnz * sizeof(int);
   int r = 0;
-  if ((r = pthip_alloc(ib, &keys)) || (r = pthip_alloc(ib, &vals)) || (r = pthip_alloc(ib, &keys2)) || (r = pthip_alloc(ib, &vals2)) ||
-      (r = pthip_alloc(ib, &rowid)) || (r = pthip_alloc((size_t)(n + 1) * sizeof(int), &counts)) ||
-      (r = pthip_alloc((size_t)256 * nb * sizeof(int), &hist)) || (r = pthip_alloc(((size_t)256 * nb + 1) * sizeof(int), &offs)))
+  if ((r = mem.alloc(ib, &keys)) || (r = mem.alloc(ib, &vals)) || (r = mem.alloc(ib, &keys2)) || (r = mem.alloc(ib, &vals2)) ||
+      (r = mem.alloc(ib, &rowid)) || (r = mem.alloc((size_t)(n + 1) * sizeof(int), &counts)) ||
+      (r = mem.alloc((size_t)256 * nb * sizeof(int), &hist)) || (r = mem.alloc(((size_t)256 * nb + 1) * sizeof(int), &offs)))
     return r;
   PTHIP_CHECK(pthip::memset_async(counts, 0, (size_t)(n + 1) * sizeof(int), st));
   PTHIP_KLAUNCH(tr_keys_kernel, dim3(grid_for(nnz, BLOCK)), dim3(BLOCK), 0, st, rows, n, nnz, (const int*)ind, (const int*)indptr,
@@ -374,9 +374,7 @@ int transpose_t(long long rows, long long n, long long nnz, const void* data, co
   // the valid entries come first (the sentinel sorts last); at most nnz of them
   PTHIP_KLAUNCH(tr_place_kernel<T>, dim3(grid_for(nnz, BLOCK)), dim3(BLOCK), 0, st, nnz, (const int*)vals, (const int*)rowid,
                 (const T*)data, (T*)data_out, (int*)ind_out);
-  r = pthip::post_launch("csr_transpose");
-  for (void* p : {keys, vals, keys2, vals2, rowid, counts, hist, offs}) pthip_free(p);
-  return r;
+  return pthip::post_launch("csr_transpose");
 }
 
 // ---- SDDMM: out[e] = (data ? data[e] : 1) * sum_j P[row(e), j] * Q[col(e), j] ---------------------------
@@ -578,14 +576,14 @@ extern "C" int pthip_csr_fromdense_count(int dtype, int64_t rows, int64_t n, con
     PTHIP_CHECK(pthip::memset_async(indptr, 0, sizeof(int), st));
     return 0;
   }
+  pthip::Scratch mem;
   void* counts = nullptr;
-  int r = pthip_alloc((size_t)rows * sizeof(int), &counts);
+  int r = mem.alloc((size_t)rows * sizeof(int), &counts);
   if (r) return r;
   PTHIP_SPARSE_DISPATCH(dtype, {
     PTHIP_KLAUNCH(fromdense_count_kernel<T>, dim3(grid_for(rows, BLOCK / 64)), dim3(BLOCK), 0, st, rows, n, (const T*)x, sx0, sx1,
                   (int*)counts);
     r = exclusive_scan_i32((const int*)counts, rows, (int*)indptr, st);
-    pthip_free(counts);
     return r ? r : pthip::post_launch("csr_fromdense_count");
   })
 }

@@ -498,7 +498,7 @@ int run_tiers(const Job<T>& j, const Layout& l, void* ws, hipStream_t st) {
   static_assert(lds_g <= (size_t)pthip::kLdsPerCU && 4 * lds_w <= (size_t)pthip::kLdsPerCU, "tier bounds against the LDS of a CU");
   auto kw = hash_kernel<T, WAVE, 2 * kWaveUb, VALUES>;
   auto kg = hash_kernel<T, BLOCK, 2 * kWgUb, VALUES>;
-  PTHIP_CHECK(hipFuncSetAttribute((const void*)kg, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_g));
+  if (int r = pthip::lds_opt_in((const void*)kg, lds_g)) return r;
   PTHIP_KLAUNCH(kw, dim3(grid_for(j.rows, BLOCK / WAVE, 8 * pthip::kNumCU)), dim3(BLOCK), lds_w, st, j, 0);
   PTHIP_KLAUNCH(kg, dim3(grid_for(j.rows, 1, pthip::kNumCU)), dim3(BLOCK), lds_g, st, j, 1);
   if (l.wgs > 0) {

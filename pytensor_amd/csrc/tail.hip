@@ -78,13 +78,14 @@ extern "C" int pthip_join_probe(int iters, int* bad_out) {
   if (r) return r;
   hipStream_t s0 = pthip::ctx().streams[0], s1 = pthip::ctx().streams[1];
   constexpr int N = 1 << 18;  // 1 MB: every L2 channel of every XCD
-  void* mem = nullptr;
-  if ((r = pthip_alloc((size_t)N * 4 + 256, &mem))) return r;
-  unsigned* buf = (unsigned*)mem;
-  int* word = (int*)((char*)mem + (size_t)N * 4);
+  pthip::Scratch mem;  // (goes back to the pool at the return below: after the drain on failure)
+  void* scratch = nullptr;
+  if ((r = mem.alloc((size_t)N * 4 + 256, &scratch))) return r;
+  unsigned* buf = (unsigned*)scratch;
+  int* word = (int*)((char*)scratch + (size_t)N * 4);
   int* bad = word + 16;
   hipEvent_t ev = nullptr;
-  // every exit path gives the buffer and the event back (the early returns of PTHIP_CHECK leaked both)
+  // every exit path gives the event back (the early returns of PTHIP_CHECK leaked it)
   auto run = [&]() -> int {
     PTHIP_CHECK(hipEventCreateWithFlags(&ev, hipEventDisableTiming));
     PTHIP_CHECK(hipMemsetAsync(word, 0, 128, s0));
@@ -113,8 +114,7 @@ extern "C" int pthip_join_probe(int iters, int* bad_out) {
     (void)hipStreamSynchronize(s1);
   }
   if (ev) (void)hipEventDestroy(ev);
-  const int rf = pthip_free(mem);
-  return r ? r : rf;
+  return r;
 }
 
 // the last launch of a plan's latency-chain segment (include/pthip.h)
