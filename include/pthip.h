@@ -258,6 +258,11 @@ int pthip_hgemm(int64_t batch, int64_t M, int64_t N, int64_t K, const void* A, i
  * inner product of two vectors.  One launch. */
 int pthip_hgemv(int64_t M, int64_t K, const void* A, int64_t sA0, int64_t sA1, const void* x,
                 int64_t sx, void* out);
+/* Splits of K that pthip_hgemm / pthip_hgemv use for a shape (1: not split).  A product with few output
+ * tiles (row blocks) and a deep K is cut into S ranges of K whose fp32 partial sums go through pool scratch;
+ * the last workgroup of a tile to arrive adds them in ascending order and rounds once, in the same launch. */
+int64_t pthip_hgemm_splits(int64_t batch, int64_t M, int64_t N, int64_t K);
+int64_t pthip_hgemv_splits(int64_t M, int64_t K, int64_t sA0, int64_t sA1);
 /* Loop-constant right operand of a skinny product (the recurrent weights of a Scan step:
  * Dot22/Gemm, blas/gemm.py:76,248, whose left operand has a few hundred rows at most), repacked
  * once per evaluation into the MFMA operand order the generated product+epilogue kernels stream:

@@ -30,6 +30,15 @@
 //   two passes.  (Lanes along the row groups alone would coalesce the global loads better and put 8 lanes on a bank.)
 //   Without 16-byte alignment (pointer, leading dimension or batch stride), and on tiles that cross M, N or K, the
 //   same registers are filled by 2-byte loads with bounds checks and zero fill.
+//
+// Split-K (few tiles, deep K): the walk runs over UNITS (batch item, tile, split s of S) instead of tiles; a unit is a
+// contiguous range of K stages (balanced: the ranges differ by at most one stage, none is empty, the partial stage is
+// in the last one).  A unit stores its fp32 accumulators to a slab of its own in accumulator-register order (register
+// (i, j, r) of thread t at [(i*NJ + j)*16 + r][t]: every store instruction of a workgroup writes 256 consecutive
+// floats, no LDS transpose), fences at device scope and takes a ticket of its tile.  The workgroup that draws S - 1
+// puts the ticket back to 0, reads the S slabs back with the same mapping, adds them in ascending s — whoever arrived
+// last, so the bits do not depend on the arrival order — rounds once and stores through the epilogue.  Nobody waits:
+// a workgroup that is not last goes on to its next unit.  hgemm_splits() holds the rule for S.
 #include "common.h"
 #include "wave_device.h"
 
@@ -134,12 +143,22 @@ __device__ __forceinline__ hbits to_half_bits(float x) {
   return u.b;
 }
 
-// Workgroups walk the (batch x tile) space with stride gridDim.x.  SKINNY: tile 64 x 128, the four waves side by side.
-template <bool AKC, bool BKC, bool SKINNY>
+// What the split kernel is given beyond the unsplit one (whose arguments stay what they were): S > 1 splits per tile,
+// one TM x HN fp32 slab per unit, one ticket word per tile.
+template <bool SPLIT> struct HSplitArgs {};
+template <> struct HSplitArgs<true> {
+  int S;
+  float* slabs;
+  int* tickets;
+};
+
+// Workgroups walk the (batch x tile x split) space with stride gridDim.x.  SKINNY: tile 64 x 128, the four waves side
+// by side.
+template <bool AKC, bool BKC, bool SKINNY, bool SPLIT>
 __global__ __launch_bounds__(BLOCK, 2) void hgemm_kernel(
     hbits* __restrict__ out, const hbits* __restrict__ A, const hbits* __restrict__ B, long long M, long long N,
     long long K, long long lda, long long ldb, long long sAb, long long sBb, long long tiles_m, long long tiles_n,
-    long long batch, int vecA, int vecB) {
+    long long batch, int vecA, int vecB, HSplitArgs<SPLIT> sp) {
   constexpr int TM = SKINNY ? 64 : 128;
   constexpr int NJ = SKINNY ? 1 : 2;
   using SA = HStage<AKC, TM>;
@@ -147,15 +166,28 @@ __global__ __launch_bounds__(BLOCK, 2) void hgemm_kernel(
   extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
   hbits* As = (hbits*)smem_raw;   // [2][SA::SIZE]
   hbits* Bs = As + 2 * SA::SIZE;  // [2][SB::SIZE]
-  const long long nt = tiles_m * tiles_n, total = nt * batch;
+  __shared__ int s_last;
+  int S = 1;
+  if constexpr (SPLIT) S = sp.S;
+  const long long nt = tiles_m * tiles_n, total = nt * batch * S;
   const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
   const int wm0 = SKINNY ? 0 : (w >> 1) * 64, wn0 = SKINNY ? w * 32 : (w & 1) * 64;
   const long long nk = K > 0 ? (K + HK - 1) / HK : 1;  // K = 0: one stage of zero fill
-  auto coords = [&](long long L, long long& m0, long long& n0, long long& bz) {
+  // unit L: its tile origin, batch item, unit id u = (bz * nt + tile) * S + s and stage range [kt0, kt1)
+  auto coords = [&](long long L, long long& m0, long long& n0, long long& bz, long long& u, long long& kt0, long long& kt1) {
     long long pid = L;
     if (total % 8 == 0) {  // XCD x (workgroup L runs on XCD L % 8) walks the contiguous range [x*total/8, (x+1)*total/8)
       const long long per = total / 8;
       pid = (L % 8) * per + L / 8;
+    }
+    u = pid;
+    kt0 = 0;
+    kt1 = nk;
+    if constexpr (SPLIT) {  // the splits of a tile are neighbours in the walk: they run at the same time
+      const long long s = pid % S, each = nk / S, rem = nk % S;
+      pid /= S;
+      kt0 = s * each + (s < rem ? s : rem);
+      kt1 = kt0 + each + (s < rem ? 1 : 0);
     }
     bz = pid / nt;
     pid -= bz * nt;
@@ -164,12 +196,12 @@ __global__ __launch_bounds__(BLOCK, 2) void hgemm_kernel(
   };
   long long L = blockIdx.x;
   if (L >= total) return;
-  long long m0, n0, bz;
-  coords(L, m0, n0, bz);
+  long long m0, n0, bz, u, kt0, kt1;
+  coords(L, m0, n0, bz, u, kt0, kt1);
   SA sa;
   SB sb;
-  sa.load(A + bz * sAb, lda, m0, 0, M, K, vecA);
-  sb.load(B + bz * sBb, ldb, n0, 0, N, K, vecB);
+  sa.load(A + bz * sAb, lda, m0, kt0 * HK, M, K, vecA);
+  sb.load(B + bz * sBb, ldb, n0, kt0 * HK, N, K, vecB);
   sa.store(As);
   sb.store(Bs);
   __syncthreads();
@@ -177,8 +209,8 @@ __global__ __launch_bounds__(BLOCK, 2) void hgemm_kernel(
   for (;;) {
     const long long Ln = L + gridDim.x;
     const bool has_next = Ln < total;
-    long long m1 = 0, n1 = 0, b1 = 0;
-    if (has_next) coords(Ln, m1, n1, b1);
+    long long m1 = 0, n1 = 0, b1 = 0, u1 = 0, kn0 = 0, kn1 = 0;
+    if (has_next) coords(Ln, m1, n1, b1, u1, kn0, kn1);
     float16_t acc[2][NJ];
 #pragma unroll
     for (int i = 0; i < 2; i++)
@@ -188,11 +220,13 @@ __global__ __launch_bounds__(BLOCK, 2) void hgemm_kernel(
         for (int r = 0; r < 16; r++) acc[i][j][r] = 0.f;
     const hbits* Ab = A + bz * sAb;
     const hbits* Bb = B + bz * sBb;
-    for (long long kt = 0; kt < nk; kt++) {
-      const bool more = kt + 1 < nk;
-      if (more || has_next) {  // the next stage of this tile, or the next tile's first one behind this tile's last MFMAs
-        sa.load(more ? Ab : A + b1 * sAb, lda, more ? m0 : m1, more ? (kt + 1) * HK : 0, M, K, vecA);
-        sb.load(more ? Bb : B + b1 * sBb, ldb, more ? n0 : n1, more ? (kt + 1) * HK : 0, N, K, vecB);
+    // (constants in the unsplit kernel, which then compiles to the registers and spills it had before there were units)
+    const long long lo = SPLIT ? kt0 : 0, hi = SPLIT ? kt1 : nk, next_k = SPLIT ? kn0 * HK : 0;
+    for (long long kt = lo; kt < hi; kt++) {
+      const bool more = kt + 1 < hi;
+      if (more || has_next) {  // the next stage of this unit, or the next unit's first one behind this unit's last MFMAs
+        sa.load(more ? Ab : A + b1 * sAb, lda, more ? m0 : m1, more ? (kt + 1) * HK : next_k, M, K, vecA);
+        sb.load(more ? Bb : B + b1 * sBb, ldb, more ? n0 : n1, more ? (kt + 1) * HK : next_k, N, K, vecB);
       }
       const hbits* as = As + buf * SA::SIZE;
       const hbits* bs = Bs + buf * SB::SIZE;
@@ -216,43 +250,112 @@ __global__ __launch_bounds__(BLOCK, 2) void hgemm_kernel(
       __syncthreads();
       buf ^= 1;
     }
+    bool finish = true;  // workgroup-uniform
+    if constexpr (SPLIT) {
+      constexpr int SLAB = TM * HN;
+      float* mine = sp.slabs + u * SLAB + threadIdx.x;
+#pragma unroll
+      for (int i = 0; i < 2; i++)
+#pragma unroll
+        for (int j = 0; j < NJ; j++)
+#pragma unroll
+          for (int r = 0; r < 16; r++) mine[((i * NJ + j) * 16 + r) * BLOCK] = acc[i][j][r];
+      __threadfence();
+      __syncthreads();
+      if (threadIdx.x == 0) s_last = atomicAdd(sp.tickets + u / S, 1) == S - 1;
+      __syncthreads();
+      finish = s_last;  // (the next write of s_last is behind the barriers of the next unit's stages)
+      if (finish) {     // the last arriver of this tile: every slab is in memory
+        if (threadIdx.x == 0) __hip_atomic_store(sp.tickets + u / S, 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        __threadfence();
+        const float* all = sp.slabs + (u / S) * S * SLAB + threadIdx.x;
+        for (int s = 0; s < S; s++)
+#pragma unroll
+          for (int i = 0; i < 2; i++)
+#pragma unroll
+            for (int j = 0; j < NJ; j++)
+#pragma unroll
+              for (int r = 0; r < 16; r++) {
+                const float v = all[(long long)s * SLAB + ((i * NJ + j) * 16 + r) * BLOCK];
+                acc[i][j][r] = s == 0 ? v : acc[i][j][r] + v;
+              }
+      }
+    }
     // epilogue: one rounding per element, in registers.  A lane holds single columns (col = l&31), so a store
     // instruction writes two runs of 32 consecutive halves (64 bytes, rows 4 apart): as wide as the layout allows.
     hbits* ob = out + bz * M * N;
     const bool interior = m0 + TM <= M && n0 + HN <= N;  // workgroup-uniform: unconditional stores
+    if (finish) {
 #pragma unroll
-    for (int i = 0; i < 2; i++)
+      for (int i = 0; i < 2; i++)
 #pragma unroll
-      for (int j = 0; j < NJ; j++)
+        for (int j = 0; j < NJ; j++)
 #pragma unroll
-        for (int r = 0; r < 16; r++) {
-          const long long row = m0 + wm0 + i * 32 + (r & 3) + 8 * (r >> 2) + 4 * (lane >> 5);
-          const long long col = n0 + wn0 + j * 32 + (lane & 31);
-          if (interior || (row < M && col < N)) ob[row * N + col] = to_half_bits(acc[i][j][r]);
-        }
+          for (int r = 0; r < 16; r++) {
+            const long long row = m0 + wm0 + i * 32 + (r & 3) + 8 * (r >> 2) + 4 * (lane >> 5);
+            const long long col = n0 + wn0 + j * 32 + (lane & 31);
+            if (interior || (row < M && col < N)) ob[row * N + col] = to_half_bits(acc[i][j][r]);
+          }
+    }
     if (!has_next) break;
     L = Ln;
     m0 = m1;
     n0 = n1;
     bz = b1;
+    u = u1;
+    kt0 = kn0;
+    kt1 = kn1;
   }
+}
+
+// Splits per tile.  1 (the unsplit kernel) when the tiles fill the resident grid on their own or K is shallow; otherwise
+// as many as fill it, each at least H_MIN_STAGES stages deep, H_MAX_SPLITS at the most.  A split costs one slab written
+// and read back (64 or 32 KB through L2), about what two stages of operands cost (32 / 24 KB each), and the finisher
+// adds the S slabs of its tile alone: profiles/hgemm.md has the numbers behind both constants.  Units stay below
+// resident + tiles < 1024 (slabs: 64 MB at the most) and tickets below resident (pthip_ticket_slots takes 8192).
+constexpr long long H_MIN_STAGES = 8, H_MAX_SPLITS = 32;
+
+long long hgemm_splits(long long batch, long long M, long long N, long long K) {
+  if (batch <= 0 || M <= 0 || N <= 0) return 1;
+  const long long TM = M <= 64 ? 64 : 128;
+  const long long tiles = ((M + TM - 1) / TM) * ((N + HN - 1) / HN) * batch, nk = (K + HK - 1) / HK;
+  const long long resident = (long long)pthip::kNumCU * 2;
+  if (tiles >= resident || nk < 2 * H_MIN_STAGES) return 1;
+  long long S = (resident + tiles - 1) / tiles;
+  if (S > nk / H_MIN_STAGES) S = nk / H_MIN_STAGES;
+  if (S > H_MAX_SPLITS) S = H_MAX_SPLITS;
+  return S;
 }
 
 template <bool AKC, bool BKC, bool SKINNY>
 int hgemm_launch(long long batch, long long M, long long N, long long K, const hbits* A, long long sAb, long long lda,
                  const hbits* B, long long sBb, long long ldb, hbits* out) {
   constexpr int TM = SKINNY ? 64 : 128;
-  auto k = hgemm_kernel<AKC, BKC, SKINNY>;
+  const long long S = hgemm_splits(batch, M, N, K);
+  const void* k = S > 1 ? (const void*)hgemm_kernel<AKC, BKC, SKINNY, true> : (const void*)hgemm_kernel<AKC, BKC, SKINNY, false>;
   const size_t shmem = (size_t)(2 * HStage<AKC, TM>::SIZE + 2 * HStage<BKC, HN>::SIZE) * sizeof(hbits);
-  if (int r = pthip::lds_opt_in((const void*)k, shmem)) return r;
-  const long long tiles_m = (M + TM - 1) / TM, tiles_n = (N + HN - 1) / HN, total = tiles_m * tiles_n * batch;
-  const long long resident = (long long)pthip::kNumCU * 2;
+  if (int r = pthip::lds_opt_in(k, shmem)) return r;
+  const long long tiles_m = (M + TM - 1) / TM, tiles_n = (N + HN - 1) / HN, tiles = tiles_m * tiles_n * batch;
+  const long long total = tiles * S, resident = (long long)pthip::kNumCU * 2;
   const long long grid = total < resident ? total : resident;
   // 16-byte loads: pointer, leading dimension and batch stride all multiples of 8 halves
   const int vecA = (lda % 8 == 0) && (((uintptr_t)A) % 16 == 0) && (sAb % 8 == 0);
   const int vecB = (ldb % 8 == 0) && (((uintptr_t)B) % 16 == 0) && (sBb % 8 == 0);
-  PTHIP_KLAUNCH(k, dim3((unsigned)grid), dim3(BLOCK), shmem, pthip::ctx().stream, out, A, B, M, N, K, lda, ldb, sAb, sBb,
-                tiles_m, tiles_n, batch, vecA, vecB);
+  pthip::Scratch mem;  // (back to the pool at the return: reuse is stream-ordered behind this launch)
+  void* slabs = nullptr;
+  void* tickets = nullptr;
+  if (S > 1) {
+    if (int r = mem.alloc((size_t)total * TM * HN * sizeof(float), &slabs)) return r;
+    if (int r = pthip_ticket_slots((int)tiles, &tickets)) return r;
+  }
+  if (S > 1) {
+    const HSplitArgs<true> sp{(int)S, (float*)slabs, (int*)tickets};
+    PTHIP_KLAUNCH((hgemm_kernel<AKC, BKC, SKINNY, true>), dim3((unsigned)grid), dim3(BLOCK), shmem, pthip::ctx().stream, out, A, B, M, N,
+                  K, lda, ldb, sAb, sBb, tiles_m, tiles_n, batch, vecA, vecB, sp);
+    return pthip::post_launch("hgemm(split-K)");
+  }
+  PTHIP_KLAUNCH((hgemm_kernel<AKC, BKC, SKINNY, false>), dim3((unsigned)grid), dim3(BLOCK), shmem, pthip::ctx().stream, out, A, B, M, N,
+                K, lda, ldb, sAb, sBb, tiles_m, tiles_n, batch, vecA, vecB, HSplitArgs<false>{});
   return pthip::post_launch("hgemm");
 }
 
@@ -265,8 +368,27 @@ __device__ __forceinline__ float h2f(hbits b) {
   return (float)u.h;
 }
 
-// Row layout: G lanes per row (64: a wave per row; 8: eight short rows per wave).  A lane takes 8 consecutive k per
-// step (one 16-byte load when VEC), adds its products in ascending k, and the G partial sums meet in group_sum's tree.
+// Lane g of the G lanes of a row, over k in [k0, k1): 8 consecutive k per step (one 16-byte load when VEC; k0 is a
+// multiple of 8 G, so the loads keep the row's alignment), products added in ascending k.
+template <int G, bool VEC>
+__device__ __forceinline__ float hgemv_lane_sum(const hbits* __restrict__ a, const hbits* __restrict__ x, int g,
+                                                long long k0, long long k1, long long sA1, long long sx) {
+  float acc = 0.f;
+  for (long long k = k0 + g * 8; k < k1; k += G * 8) {
+    if (VEC && k + 8 <= k1) {
+      Vec8 av;
+      av.q = *(const uint4*)(a + k);
+#pragma unroll
+      for (int e = 0; e < 8; e++) acc = fmaf(h2f(av.h[e]), h2f(x[(k + e) * sx]), acc);
+    } else {
+      for (int e = 0; e < 8 && k + e < k1; e++) acc = fmaf(h2f(a[(k + e) * sA1]), h2f(x[(k + e) * sx]), acc);
+    }
+  }
+  return acc;
+}
+
+// Row layout: G lanes per row (64: a wave per row; 8: eight short rows per wave); the G partial sums of
+// hgemv_lane_sum meet in group_sum's tree.
 template <int G, bool VEC>
 __global__ __launch_bounds__(BLOCK) void hgemv_row_kernel(hbits* __restrict__ out, const hbits* __restrict__ A,
                                                           const hbits* __restrict__ x, long long M, long long K,
@@ -276,21 +398,57 @@ __global__ __launch_bounds__(BLOCK) void hgemv_row_kernel(hbits* __restrict__ ou
   for (long long m = (long long)blockIdx.x * RPB + threadIdx.x / G; m - threadIdx.x / G < M; m += (long long)gridDim.x * RPB) {
     // (the loop bound is wave-uniform: every lane of a wave reaches the shuffles of group_sum)
     float acc = 0.f;
-    if (m < M) {
-      const hbits* a = A + m * sA0;
-      for (long long k = g * 8; k < K; k += G * 8) {
-        if (VEC && k + 8 <= K) {
-          Vec8 av;
-          av.q = *(const uint4*)(a + k);
-#pragma unroll
-          for (int e = 0; e < 8; e++) acc = fmaf(h2f(av.h[e]), h2f(x[(k + e) * sx]), acc);
-        } else {
-          for (int e = 0; e < 8 && k + e < K; e++) acc = fmaf(h2f(a[(k + e) * sA1]), h2f(x[(k + e) * sx]), acc);
-        }
-      }
-    }
+    if (m < M) acc = hgemv_lane_sum<G, VEC>(A + m * sA0, x, g, 0, K, sA1, sx);
     acc = wave::group_sum<G>(acc);
     if (g == 0 && m < M) out[m] = to_half_bits(acc);
+  }
+}
+
+// The hand-over shared by the two split matrix-vector kernels: the block has stored its partial sums; the one that
+// draws S - 1 from its row block's ticket puts the ticket back and goes on (true), every other block is done.
+__device__ __forceinline__ bool hgemv_last_arriver(int* ticket, int S, int* s_last) {
+  __threadfence();
+  __syncthreads();
+  if (threadIdx.x == 0) *s_last = atomicAdd(ticket, 1) == S - 1;
+  __syncthreads();
+  if (!*s_last) return false;
+  if (threadIdx.x == 0) __hip_atomic_store(ticket, 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  __threadfence();
+  return true;
+}
+
+// Row layout, few rows and a deep K: block (row block rb, split s) takes k in [s * chunk, (s + 1) * chunk) of RPB rows
+// (4: a wave per row; 1: the whole block on one row, so that an inner product fills every wave slot) and stores RPB
+// fp32 partial sums at slabs[rb][s][row].  The last arriver of the row block adds them in a fixed order (wave `row`:
+// lane l adds s = l, l + 64, ... ascending, then group_sum's tree) and rounds once.
+template <int RPB, bool VEC>
+__global__ __launch_bounds__(BLOCK) void hgemv_row_split_kernel(hbits* __restrict__ out, const hbits* __restrict__ A,
+                                                                const hbits* __restrict__ x, long long M, long long K,
+                                                                long long sA0, long long sA1, long long sx, int S,
+                                                                long long chunk, float* slabs, int* tickets) {
+  constexpr int G = BLOCK / RPB;
+  __shared__ float s_w[BLOCK / 64];
+  __shared__ int s_last;
+  const long long rb = blockIdx.x / S;
+  const int s = blockIdx.x % S, g = threadIdx.x % G, row = threadIdx.x / G;
+  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+  const long long m = rb * RPB + row, k0 = s * chunk, k1 = k0 + chunk < K ? k0 + chunk : K;
+  float acc = 0.f;
+  if (m < M) acc = hgemv_lane_sum<G, VEC>(A + m * sA0, x, g, k0, k1, sA1, sx);
+  acc = wave::group_sum<64>(acc);
+  if constexpr (G > 64) {  // the four waves of the row, added in wave order
+    if (lane == 0) s_w[w] = acc;
+    __syncthreads();
+    acc = ((s_w[0] + s_w[1]) + s_w[2]) + s_w[3];
+  }
+  float* slab = slabs + rb * S * RPB;
+  if (g == 0) slab[s * RPB + row] = acc;
+  if (!hgemv_last_arriver(tickets + rb, S, &s_last)) return;
+  if (w < RPB) {
+    float t = 0.f;
+    for (int p = lane; p < S; p += 64) t += slab[p * RPB + w];
+    t = wave::group_sum<64>(t);
+    if (lane == 0 && rb * RPB + w < M) out[rb * RPB + w] = to_half_bits(t);
   }
 }
 
@@ -318,7 +476,73 @@ __global__ __launch_bounds__(BLOCK) void hgemv_col_kernel(hbits* __restrict__ ou
   }
 }
 
+// Column layout, few 64-column blocks and a deep K: block (column block cb, split s) takes k in [s * chunk,
+// (s + 1) * chunk), its four waves k = k0 + w, k0 + w + 4, ...; their sums, added in wave order, go to
+// slabs[cb][s][lane].  The last arriver of the column block adds the S partial sums of a lane in ascending s.
+__global__ __launch_bounds__(BLOCK) void hgemv_col_split_kernel(hbits* __restrict__ out, const hbits* __restrict__ A,
+                                                                const hbits* __restrict__ x, long long M, long long K,
+                                                                long long sA1, long long sx, int S, long long chunk,
+                                                                float* slabs, int* tickets) {
+  __shared__ float s_part[BLOCK / 64][64];
+  __shared__ int s_last;
+  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+  const long long cb = blockIdx.x / S;
+  const int s = blockIdx.x % S;
+  const long long m = cb * 64 + lane, k0 = s * chunk, k1 = k0 + chunk < K ? k0 + chunk : K;
+  float acc = 0.f;
+  if (m < M)
+    for (long long k = k0 + w; k < k1; k += BLOCK / 64) acc = fmaf(h2f(A[k * sA1 + m]), h2f(x[k * sx]), acc);
+  s_part[w][lane] = acc;
+  __syncthreads();
+  float* slab = slabs + cb * S * 64;
+  if (w == 0) {
+    float t = s_part[0][lane];
+#pragma unroll
+    for (int p = 1; p < BLOCK / 64; p++) t += s_part[p][lane];
+    slab[s * 64 + lane] = t;
+  }
+  if (!hgemv_last_arriver(tickets + cb, S, &s_last)) return;
+  if (w == 0 && m < M) {
+    float t = slab[lane];
+    for (int p = 1; p < S; p++) t += slab[p * 64 + lane];
+    out[m] = to_half_bits(t);
+  }
+}
+
+// How pthip_hgemv runs a product: the layout, and the split of k when the row (column) blocks are few and K is deep.
+// S = 1: the unsplit kernels.  Otherwise S blocks per row block, as many as fill H_GEMV_BLOCKS, each at least four
+// steps of its lanes deep (row layout: chunks are multiples of 8 G, so the vector loads keep their alignment).
+struct HgemvPlan {
+  bool col;
+  int rpb;          // row layout: rows per block of the split kernel (1 below four rows)
+  long long units;  // row blocks / 64-column blocks
+  long long S, chunk;
+};
+constexpr long long H_GEMV_BLOCKS = (long long)pthip::kNumCU * 4;
+
+HgemvPlan hgemv_plan(long long M, long long K, long long sA0, long long sA1) {
+  HgemvPlan p;
+  if (K <= 1) sA1 = 1;
+  p.col = sA0 == 1 && sA1 != 1 && M > 1;
+  p.rpb = M < 4 ? 1 : 4;
+  p.units = p.col ? (M + 63) / 64 : (M + p.rpb - 1) / p.rpb;
+  const long long step = p.col ? BLOCK / 64 : (long long)(BLOCK / p.rpb) * 8;  // k per pass of the block's lanes
+  const long long steps = (K + step - 1) / step, min_steps = p.col ? 64 : 4;
+  p.S = 1;
+  p.chunk = K;
+  if (M <= 0 || p.units * 2 > H_GEMV_BLOCKS || steps < 2 * min_steps) return p;
+  long long S = (H_GEMV_BLOCKS + p.units - 1) / p.units;
+  if (S > steps / min_steps) S = steps / min_steps;
+  p.chunk = (steps + S - 1) / S * step;
+  p.S = (K + p.chunk - 1) / p.chunk;  // no empty chunk
+  return p;
+}
+
 }  // namespace
+
+extern "C" int64_t pthip_hgemm_splits(int64_t batch, int64_t M, int64_t N, int64_t K) { return hgemm_splits(batch, M, N, K); }
+
+extern "C" int64_t pthip_hgemv_splits(int64_t M, int64_t K, int64_t sA0, int64_t sA1) { return hgemv_plan(M, K, sA0, sA1).S; }
 
 extern "C" int pthip_hgemm(int64_t batch, int64_t M, int64_t N, int64_t K, const void* A, int64_t sAb, int64_t sA0,
                            int64_t sA1, const void* B, int64_t sBb, int64_t sB0, int64_t sB1, void* out) {
@@ -364,6 +588,28 @@ extern "C" int pthip_hgemv(int64_t M, int64_t K, const void* A, int64_t sA0, int
   hbits* o = (hbits*)out;
   hipStream_t st = pthip::ctx().stream;
   const long long max_blocks = (long long)pthip::kNumCU * 8;
+  const HgemvPlan p = hgemv_plan(M, K, sA0, sA1);
+  if (p.S > 1) {  // few row blocks, deep K: S blocks per row block, finished by the last arriver in the same launch
+    pthip::Scratch mem;
+    void* slabs = nullptr;
+    void* tickets = nullptr;
+    if (int r = mem.alloc((size_t)(p.units * p.S * (p.col ? 64 : p.rpb)) * sizeof(float), &slabs)) return r;
+    if (int r = pthip_ticket_slots((int)p.units, &tickets)) return r;
+    const dim3 grid((unsigned)(p.units * p.S));
+    if (p.col) {
+      PTHIP_KLAUNCH(hgemv_col_split_kernel, grid, dim3(BLOCK), 0, st, o, a, xv, (long long)M, (long long)K, (long long)sA1,
+                    (long long)sx, (int)p.S, p.chunk, (float*)slabs, (int*)tickets);
+      return pthip::post_launch("hgemv(col, split-K)");
+    }
+    const bool vec = sA1 == 1 && ((uintptr_t)A) % 16 == 0 && (sA0 % 8 == 0 || M == 1);
+#define GO(R, V)                                                                                                            \
+  PTHIP_KLAUNCH((hgemv_row_split_kernel<R, V>), grid, dim3(BLOCK), 0, st, o, a, xv, (long long)M, (long long)K, (long long)sA0, \
+                (long long)sA1, (long long)sx, (int)p.S, p.chunk, (float*)slabs, (int*)tickets)
+    if (p.rpb == 1) { if (vec) GO(1, true); else GO(1, false); }
+    else { if (vec) GO(4, true); else GO(4, false); }
+#undef GO
+    return pthip::post_launch("hgemv(row, split-K)");
+  }
   if (sA0 == 1 && sA1 != 1 && M > 1) {
     long long blocks = (M + 63) / 64;
     if (blocks > max_blocks) blocks = max_blocks;

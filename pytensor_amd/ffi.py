@@ -117,6 +117,8 @@ SIGNATURES = {
     "pthip_gemm_partials": (_int, [_int, _i64, _i64, _i64, _i64, _vp, _i64, _i64, _i64, _vp, _i64, _i64, _i64, _vp, _i64]),
     "pthip_hgemm": (_int, [_i64, _i64, _i64, _i64, _vp, _i64, _i64, _i64, _vp, _i64, _i64, _i64, _vp]),
     "pthip_hgemv": (_int, [_i64, _i64, _vp, _i64, _i64, _vp, _i64, _vp]),
+    "pthip_hgemm_splits": (_i64, [_i64, _i64, _i64, _i64]),
+    "pthip_hgemv_splits": (_i64, [_i64, _i64, _i64, _i64]),
     "pthip_pack_b16": (_int, [_int, _i64, _i64, _vp, _i64, _i64, _vp]),
     "pthip_ger": (_int, [_int, _i64, _i64, _dbl, _vp, _i64, _i64, _vp, _i64, _vp, _i64, _vp]),
     "pthip_potrf": (_int, [_int, _int, _i64, _i64, _vp, _vp]),

@@ -33,7 +33,11 @@ def timed(lib, fn, reps):
     return ms.value / reps
 
 
-HALF_SHAPES = [(1, 4096, 4096, 4096), (512, 256, 256, 256), (1, 64, 4096, 4096)]
+# the last three are deep-K shapes with few tiles (split-K): 512 x 512 x 65536 in orientation TN is the weight gradient
+# x.T @ gy of a 512 -> 512 dense layer at batch 65536
+HALF_SHAPES = [(1, 4096, 4096, 4096), (512, 256, 256, 256), (1, 64, 4096, 4096), (1, 512, 512, 65536), (1, 16, 4096, 4096),
+               (1, 64, 1024, 32768)]
+HALF_GEMV = [(4, 10 ** 6), (1, 10 ** 7)]  # (M, K), row layout: four long rows, the inner product
 ORIENT = (("NN", False, False), ("NT", False, True), ("TN", True, False), ("TT", True, True))
 
 
@@ -72,9 +76,21 @@ def half_rows(lib):
             ms_h, ms_c = min(r[0] for r in runs), min(r[1] for r in runs)
             tf = 2.0 * batch * M * N * K / ms_h / 1e9
             print(json.dumps({"dtype": "float16", "batch": batch, "M": M, "N": N, "K": K, "orient": tag, "hgemm_ms": round(ms_h, 4),
+                              "S": lib.pthip_hgemm_splits(batch, M, N, K),
                               "cast_sgemm_ms": round(ms_c, 4), "speedup": round(ms_c / ms_h, 2), "TFLOPs": round(tf, 1),
                               "clock_MHz": round(mhz), "peak_TFLOPs": round(peak, 1), "frac": round(tf / peak, 3),
                               "runs_ms": [[round(v, 4) for v in r] for r in runs]}), flush=True)
+    for M, K in HALF_GEMV:  # bandwidth-bound: GB/s of A and x read once
+        A = DeviceArray.from_host(rng.standard_normal((M, K)).astype(np.float16))
+        x = DeviceArray.from_host(rng.standard_normal(K).astype(np.float16))
+        out = DeviceArray.empty((M,), "float16")
+
+        def gemv():
+            ffi.check(lib.pthip_hgemv(M, K, A.ptr, K, 1, x.ptr, 1, out.ptr))
+
+        runs = [timed(lib, gemv, 20) for _ in range(2)]
+        print(json.dumps({"dtype": "float16", "op": "hgemv", "M": M, "K": K, "S": lib.pthip_hgemv_splits(M, K, K, 1), "hgemv_ms": round(min(runs), 4),
+                          "GBs": round(2.0 * (M + 1) * K / min(runs) / 1e6, 1), "runs_ms": [round(v, 4) for v in runs]}), flush=True)
 
 
 def main():
