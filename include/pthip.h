@@ -263,6 +263,17 @@ int pthip_hgemv(int64_t M, int64_t K, const void* A, int64_t sA0, int64_t sA1, c
  * the last workgroup of a tile to arrive adds them in ascending order and rounds once, in the same launch. */
 int64_t pthip_hgemm_splits(int64_t batch, int64_t M, int64_t N, int64_t K);
 int64_t pthip_hgemv_splits(int64_t M, int64_t K, int64_t sA0, int64_t sA1);
+/* float16 attention (csrc/hattention.hip): out[b] (S×Dv, contiguous, float16) =
+ * half(softmax_rows(scale · Q[b] (S×D) K[b]^T (D×T)) V[b] (T×Dv)).  The scores stay in fp32 MFMA accumulators
+ * (never in memory), the scale is applied in fp32, the softmax is online in fp32, P is rounded to half only as
+ * the operand of the second product, O / l is rounded once.  Row strides in elements, the last axis of every
+ * operand contiguous; batch stride 0 = shared.  `scale`: a float16 scalar in DEVICE memory (read by the kernel:
+ * no host read) or NULL for 1; scale_div = 1 divides by it.  Any S, T >= 1; D, Dv <= pthip_hattention_max_d().
+ * One launch, no scratch, bit-reproducible. */
+int pthip_hattention(int64_t batch, int64_t S, int64_t T, int64_t D, int64_t Dv, const void* Q, int64_t sQb,
+                     int64_t sQ0, const void* K, int64_t sKb, int64_t sK0, const void* V, int64_t sVb,
+                     int64_t sV0, const void* scale, int scale_div, void* out);
+int64_t pthip_hattention_max_d(void);
 /* Loop-constant right operand of a skinny product (the recurrent weights of a Scan step:
  * Dot22/Gemm, blas/gemm.py:76,248, whose left operand has a few hundred rows at most), repacked
  * once per evaluation into the MFMA operand order the generated product+epilogue kernels stream:
@@ -494,7 +505,8 @@ int pthip_pack(int n, const void* const* srcs, const int64_t* nbytes, const int6
 /* ---- Softmax / LogSoftmax over the last axis (pytensor/tensor/special.py:26,67; the reference
  *      inlines them into Max + Composite + Sum + Composite before fusing, rewriting/ofg.py:46-70;
  *      here one kernel, one HBM read + one write).  x, out: contiguous rows x cols; log_ = 1 for
- *      LogSoftmax.  float32 sums accumulate in double like the reference's Sum. ---- */
+ *      LogSoftmax.  float32 sums accumulate in double like the reference's Sum.  PTHIP_F16: halves are
+ *      loaded, max / exp / sum / quotient (or (x - max) - log sum) are fp32 in a fixed order, ONE rounding to half. ---- */
 int pthip_softmax(int dtype, int log_, int64_t rows, int64_t cols, const void* x, void* out);
 /* ---- round 6: log-sum-exp as one reduction, and Softmax / LogSoftmax over a NON-trailing axis.  The reference has no
  *      op for the former: pytensor/tensor/math.py logsumexp is rewritten into Max -> Composite -> Sum -> Composite

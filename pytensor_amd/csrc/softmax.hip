@@ -914,13 +914,142 @@ int lse_rows_typed(long long rows, long long cols, const void* x, void* out) {
   return pthip::post_launch("logsumexp(wave-streamed rows)");
 }
 
+// =====================================================================================================================
+// float16 rows (the hgemm rule: wider inside, one rounding).  Halves are loaded, the max, exp(x - max), the sum and the
+// quotient e * (1 / sum) — or (x - max) - log(sum) — are fp32, the result is rounded to half once.  Kernels of their
+// own, so that the float32 / float64 instantiations above stay what they were.
+//
+// G lanes per row, three sweeps over the row (the second and third hit L1 / L2), 8 halves = 16 bytes per lane and step
+// when rows and pointers are 16-byte aligned (cols % 8 == 0), single halves otherwise:
+//   G = 8    cols <= HS_SHORT: eight short rows per wave;
+//   G = 64   a wave per row;
+//   G = 256  few (< 2 * kNumCU) long (>= HS_LONG) rows: a workgroup per row, streamed in chunks of
+//            256 lanes x 8 halves; the four wave results meet in LDS in wave order.
+// The sum: a lane adds its elements in ascending order, the lanes meet in a butterfly: a fixed order.
+// =====================================================================================================================
+typedef unsigned short hbits;
+constexpr long long HS_SHORT = 64, HS_LONG = 4096;
+
+__device__ __forceinline__ float hs_float(hbits b) {
+  union { hbits b; _Float16 h; } u;
+  u.b = b;
+  return (float)u.h;
+}
+__device__ __forceinline__ hbits hs_half(float x) {
+  union { _Float16 h; hbits b; } u;
+  u.h = (_Float16)x;
+  return u.b;
+}
+union HsPack {
+  uint4 q;
+  hbits h[8];
+};
+
+template <int G, bool MAX>
+__device__ __forceinline__ float hs_group_reduce(float v, float* s_red) {
+  constexpr int W = G > 64 ? 64 : G;
+#pragma unroll
+  for (int o = W >> 1; o > 0; o >>= 1) {
+    const float t = __shfl_xor(v, o);
+    v = MAX ? nan_max(v, t) : v + t;
+  }
+  if constexpr (G > 64) {
+    __syncthreads();  // (the previous result has been read)
+    if ((threadIdx.x & 63) == 0) s_red[threadIdx.x >> 6] = v;
+    __syncthreads();
+    v = MAX ? nan_max(nan_max(nan_max(s_red[0], s_red[1]), s_red[2]), s_red[3]) : ((s_red[0] + s_red[1]) + s_red[2]) + s_red[3];
+  }
+  return v;
+}
+
+template <int G, bool LOG>
+__global__ __launch_bounds__(BLOCK) void hsoftmax_kernel(hbits* __restrict__ out, const hbits* __restrict__ x, long long rows,
+                                                         long long cols, int vec) {
+  constexpr int RPB = BLOCK / G;
+  __shared__ float s_red[BLOCK / 64];
+  const int g = threadIdx.x % G;
+  // (the loop bound is workgroup-uniform: every lane reaches the shuffles and barriers; a lane behind the last row
+  //  works on the last row and stores nothing)
+  for (long long r0 = (long long)blockIdx.x * RPB; r0 < rows; r0 += (long long)gridDim.x * RPB) {
+    const long long r = r0 + threadIdx.x / G;
+    const bool live = r < rows;
+    const hbits* xr = x + (live ? r : rows - 1) * cols;
+    hbits* orow = out + (live ? r : rows - 1) * cols;
+    float m = -__builtin_huge_valf();
+    if (vec) {
+      for (long long j = (long long)g * 8; j < cols; j += G * 8) {
+        HsPack v;
+        v.q = *(const uint4*)(xr + j);
+#pragma unroll
+        for (int e = 0; e < 8; e++) m = nan_max(m, hs_float(v.h[e]));
+      }
+    } else {
+      for (long long j = g; j < cols; j += G) m = nan_max(m, hs_float(xr[j]));
+    }
+    m = hs_group_reduce<G, true>(m, s_red);
+    float s = 0.f;
+    if (vec) {
+      for (long long j = (long long)g * 8; j < cols; j += G * 8) {
+        HsPack v;
+        v.q = *(const uint4*)(xr + j);
+#pragma unroll
+        for (int e = 0; e < 8; e++) s += expf(hs_float(v.h[e]) - m);
+      }
+    } else {
+      for (long long j = g; j < cols; j += G) s += expf(hs_float(xr[j]) - m);
+    }
+    s = hs_group_reduce<G, false>(s, s_red);
+    const float k = LOG ? logf(s) : 1.f / s;
+    if (!live) continue;
+    if (vec) {
+      for (long long j = (long long)g * 8; j < cols; j += G * 8) {
+        HsPack v;
+        v.q = *(const uint4*)(xr + j);
+#pragma unroll
+        for (int e = 0; e < 8; e++) {
+          const float d = hs_float(v.h[e]) - m;
+          v.h[e] = hs_half(LOG ? d - k : expf(d) * k);
+        }
+        *(uint4*)(orow + j) = v.q;
+      }
+    } else {
+      for (long long j = g; j < cols; j += G) {
+        const float d = hs_float(xr[j]) - m;
+        orow[j] = hs_half(LOG ? d - k : expf(d) * k);
+      }
+    }
+  }
+}
+
+int hsoftmax(int log_, long long rows, long long cols, const void* x, void* out) {
+  if (rows == 0 || cols == 0) return 0;
+  hipStream_t st = pthip::ctx().stream;
+  const int vec = cols % 8 == 0 && ((uintptr_t)x % 16) == 0 && ((uintptr_t)out % 16) == 0;
+  const long long cap = (long long)pthip::kNumCU * 8;
+#define LAUNCH_H(G, what)                                                                                                       \
+  do {                                                                                                                          \
+    long long blocks = (rows + BLOCK / G - 1) / (BLOCK / G);                                                                    \
+    if (blocks > cap) blocks = cap;                                                                                             \
+    if (log_)                                                                                                                   \
+      PTHIP_KLAUNCH((hsoftmax_kernel<G, true>), dim3((unsigned)blocks), dim3(BLOCK), 0, st, (hbits*)out, (const hbits*)x, rows, cols, vec);  \
+    else                                                                                                                        \
+      PTHIP_KLAUNCH((hsoftmax_kernel<G, false>), dim3((unsigned)blocks), dim3(BLOCK), 0, st, (hbits*)out, (const hbits*)x, rows, cols, vec); \
+    return pthip::post_launch(what);                                                                                            \
+  } while (0)
+  if (cols <= HS_SHORT) LAUNCH_H(8, "softmax(float16, eight rows per wave)");
+  if (rows < 2 * (long long)pthip::kNumCU && cols >= HS_LONG) LAUNCH_H(256, "softmax(float16, workgroup per row)");
+  LAUNCH_H(64, "softmax(float16, wave per row)");
+#undef LAUNCH_H
+}
+
 }  // namespace
 
 extern "C" int pthip_softmax(int dtype, int log_, int64_t rows, int64_t cols, const void* x, void* out) {
   PTHIP_REQUIRE_INIT();
+  if (dtype == PTHIP_F16) return hsoftmax(log_, rows, cols, x, out);
   if (dtype == PTHIP_F64) return softmax_typed<double>(log_, rows, cols, x, out);
   if (dtype == PTHIP_F32) return softmax_typed<float>(log_, rows, cols, x, out);
-  return pthip::set_error("pthip_softmax: dtype %d not supported (float32/float64 only)", dtype);
+  return pthip::set_error("pthip_softmax: dtype %d not supported (float16/float32/float64 only)", dtype);
 }
 
 // ---- round 6: log-sum-exp over the last / a middle axis, softmax over a middle axis (contiguous operands) ----------

@@ -301,6 +301,66 @@ def batched_dot(node, inputs, env):
     return [gemm_device(env, 1.0, _prep3d(x), _prep3d(y), batch=True)]
 
 
+def _rows_contiguous(x):
+    """``x`` (batch, R, C) as the attention kernel reads an operand: last axis contiguous, no negative stride"""
+    ok = all(s >= 0 for s in x.strides) and (x.strides[2] == 1 or x.shape[2] <= 1)
+    return x if ok else x.contiguous()
+
+
+def _attention_unfused(env, q, kT, v, scale, how):
+    """The chain the ``Attention`` node replaced, on its own kernels (shapes the fused kernel does not take): product,
+    scale, softmax, product, each rounded to half as the reference's nodes are."""
+    from pytensor_amd.dispatch.elemwise import launch_elemwise
+
+    s = hgemm_device(env, _prep3d(q), _prep3d(kT), batch=True)
+    if scale is not None and s.size:
+        sc = env.to_device(scale).view((1, 1, 1), (0, 0, 0))
+        body = {"in_dtypes": ["float16", "float16"], "out_dtypes": ["float16"],
+                "body": [{"op": "Mul" if how == "mul" else "TrueDiv", "in": [["i", 0], ["i", 1]], "dtype": "float16"}], "outs": [["t", 0]]}
+        s = launch_elemwise(body, [s, sc], s.shape, ["float16"], None, env)[0][0].contiguous()
+    p = DeviceArray.empty(s.shape, "float16")
+    if p.size:
+        ffi.check(env.lib.pthip_softmax(_dt(s), 0, s.shape[0] * s.shape[1], s.shape[2], s.ptr, p.ptr))
+    return hgemm_device(env, p, _prep3d(v), batch=True)
+
+
+@handler("Attention")
+def attention(node, inputs, env):
+    """``softmax(scale * q @ kT, axis=-1) @ v`` on float16 operands in one launch (attnfuse.fuse_attention,
+    csrc/hattention.hip).  Shapes are symbolic at compile time, so the layout decisions are made here from the strides:
+    ``kT`` arrives as a (.., D, T) view; when its D axis has unit stride it is K (T, D) as the kernel reads it, otherwise
+    it is copied once.  The scale stays on the device (a constant is uploaded, a runtime scalar is read by the kernel):
+    nothing is read back.  D or Dv beyond the kernel's limit, and T = 0, run the unfused chain."""
+    q, kT, v = (env.to_device(i) for i in inputs[:3])
+    scale, how = (inputs[3] if len(inputs) > 3 else None), node.params["scale"]
+    two_d = q.ndim == 2
+    if two_d:
+        q, kT, v = (x.view((1, *x.shape), (0, *x.strides)) for x in (q, kT, v))
+    (nb, S, D), (nb2, D2, T), (nb3, T2, Dv) = q.shape, kT.shape, v.shape
+    if not nb == nb2 == nb3:
+        raise TypeError(f"Inputs [{q.shape}, {kT.shape}, {v.shape}] must have the same size in axis 0")
+    if D != D2:
+        raise ValueError(f"Shape mismatch: x has {D} cols but y has {D2} rows")
+    if T != T2:
+        raise ValueError(f"Shape mismatch: x has {T} cols but y has {T2} rows")
+    if T == 0 or max(D, Dv) > int(env.lib.pthip_hattention_max_d()):
+        out = _attention_unfused(env, q, kT, v, scale, how)
+    else:
+        out = DeviceArray.empty((nb, S, Dv), "float16")
+        if out.size:
+            q, v = _rows_contiguous(q), _rows_contiguous(v)
+            k = _rows_contiguous(kT.view((nb, T, D), (kT.strides[0], kT.strides[2], kT.strides[1])))
+            sc = env.to_device(scale) if scale is not None else None
+            bs = lambda x: x.strides[0] if nb > 1 else 0
+            env.timed(
+                f"hattention_b{nb}_{S}x{T}x{D}x{Dv}",
+                lambda: ffi.check(env.lib.pthip_hattention(nb, S, T, D, Dv, q.ptr, bs(q), q.strides[1], k.ptr, bs(k), k.strides[1],
+                                                           v.ptr, bs(v), v.strides[1], sc.ptr if sc is not None else None,
+                                                           int(how == "div"), out.ptr)),
+            )
+    return [out.view(out.shape[1:], out.strides[1:]) if two_d else out]
+
+
 def _int_dot(env, x, y, out_dtype):
     """Integer ``Dot`` (no BLAS in the reference either: ``np.dot`` on integer arrays): operands
     cast to the result dtype, wrap-around arithmetic, bit-exact."""

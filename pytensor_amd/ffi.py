@@ -119,6 +119,8 @@ SIGNATURES = {
     "pthip_hgemv": (_int, [_i64, _i64, _vp, _i64, _i64, _vp, _i64, _vp]),
     "pthip_hgemm_splits": (_i64, [_i64, _i64, _i64, _i64]),
     "pthip_hgemv_splits": (_i64, [_i64, _i64, _i64, _i64]),
+    "pthip_hattention": (_int, [_i64, _i64, _i64, _i64, _i64, _vp, _i64, _i64, _vp, _i64, _i64, _vp, _i64, _i64, _vp, _int, _vp]),
+    "pthip_hattention_max_d": (_i64, []),
     "pthip_pack_b16": (_int, [_int, _i64, _i64, _vp, _i64, _i64, _vp]),
     "pthip_ger": (_int, [_int, _i64, _i64, _dbl, _vp, _i64, _i64, _vp, _i64, _vp, _i64, _vp]),
     "pthip_potrf": (_int, [_int, _int, _i64, _i64, _vp, _vp]),

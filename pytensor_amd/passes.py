@@ -10,6 +10,7 @@ Order matters:
    ``duplicate_cheap_producers`` / ``fuse_elemwise_axis_reduce`` (axisfuse.py) — reductions over SOME axes too;
 3. ``merge_sibling_reductions`` (inline.py);
 4. ``hoist_scan_seq_dots`` — sequence-only products out of ``Scan``;
+   ``fuse_attention`` (attnfuse.py) — float16 ``softmax(scale * q @ kT) @ v`` as one ``Attention`` node;
 5. ``fuse_cholesky_solve`` — Cholesky + its first triangular solve, factor kept in LDS;
    ``defer_gemm_finish`` (gemmfuse.py) — split-K finish + Gemm epilogue folded into the
    consuming elementwise kernel (also inside Scan inner graphs); ``fuse_dot_epilogue`` —
@@ -30,6 +31,7 @@ from __future__ import annotations
 
 import os
 
+from pytensor_amd.attnfuse import fuse_attention
 from pytensor_amd.axisfuse import drop_identity_elemwise, duplicate_cheap_producers, fuse_elemwise_axis_reduce, fuse_logsumexp
 from pytensor_amd.fusion import (
     fuse_cholesky_solve,
@@ -71,6 +73,7 @@ def run_pipeline(graph: Graph, fuse=True, tail=True):
             g = drop_identity_elemwise(fuse_logsumexp(g))  # log(sum(exp(x - max))) + max: one pass, the Max reductions die
     g = merge_sibling_reductions(g)
     g = hoist_scan_seq_dots(g)
+    g = fuse_attention(g)  # float16 softmax(scale * q @ kT) @ v: one launch, the scores never stored (PTHIP_ATTENTION=0: off)
     g = fuse_cholesky_solve(g)
     g = defer_gemm_finish(g)
     if os.environ.get("PTHIP_DOT_EPILOGUE", "1") != "0":

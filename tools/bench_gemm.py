@@ -2,6 +2,7 @@
 
 usage: python tools/bench_gemm.py [shape indices]
        python tools/bench_gemm.py half     (pthip_hgemm against cast + fp32 product + cast, four orientations)
+       python tools/bench_gemm.py attention  (pthip_hattention against the unfused float16 and float32 chains)
 """
 import ctypes as C
 import json
@@ -93,11 +94,57 @@ def half_rows(lib):
                           "GBs": round(2.0 * (M + 1) * K / min(runs) / 1e6, 1), "runs_ms": [round(v, 4) for v in runs]}), flush=True)
 
 
+ATTENTION_SHAPES = [(16, 1024, 1024, 64), (16, 4096, 4096, 128), (64, 128, 128, 64)]  # (batch, S, T, D = Dv)
+
+
+def attention_rows(lib):
+    """float16 attention softmax(q k^T / sqrt(D)) v: the fused kernel (pthip_hattention), this build's unfused float16
+    chain (what PTHIP_ATTENTION=0 runs: hgemm, scale, float16 softmax, hgemm) and the float32 form of the same chain
+    (what a user had to write before float16 softmax existed: fp32 products with the scale as alpha, fp32 softmax) —
+    same process, alternating, three rounds; every round's time is reported."""
+    from pytensor_amd.dispatch import blas
+    from pytensor_amd.dispatch.elemwise import _StreamEnv
+
+    env = _StreamEnv()
+    env.to_device = lambda x: x  # (every operand here is on the device already)
+    rng = np.random.default_rng(0)
+    f32 = ffi.np_dtype_code("float32")
+    for nb, S, T, D in ATTENTION_SHAPES:
+        host = [rng.standard_normal(s).astype(np.float16) for s in ((nb, S, D), (nb, T, D), (nb, T, D))]
+        q, k, v = (DeviceArray.from_host(x) for x in host)
+        q32, k32, v32 = (DeviceArray.from_host(x.astype(np.float32)) for x in host)
+        kT, kT32 = (x.view((nb, D, T), (T * D, 1, D)) for x in (k, k32))
+        scale = float(np.float16(D ** -0.5))
+        sc = DeviceArray.from_host(np.array([scale], np.float16))
+        out = DeviceArray.empty((nb, S, D), "float16")
+
+        def fused():
+            ffi.check(lib.pthip_hattention(nb, S, T, D, D, q.ptr, S * D, D, k.ptr, T * D, D, v.ptr, T * D, D, sc.ptr, 0, out.ptr))
+
+        def unfused():
+            return blas._attention_unfused(env, q, kT, v, sc, "mul")
+
+        def float32():
+            s = blas.gemm_device(env, scale, q32, kT32, batch=True)
+            p = DeviceArray.empty(s.shape, "float32")
+            ffi.check(lib.pthip_softmax(f32, 0, nb * S, T, s.ptr, p.ptr))
+            return blas.gemm_device(env, 1.0, p, v32, batch=True)
+
+        reps = 5 if S * T >= 1 << 24 else 20
+        runs = [[timed(lib, f, reps) for f in (fused, unfused, float32)] for _ in range(3)]
+        best = [min(r[i] for r in runs) for i in range(3)]
+        print(json.dumps({"op": "attention", "batch": nb, "S": S, "T": T, "D": D, "fused_ms": round(best[0], 4), "unfused_ms": round(best[1], 4),
+                          "float32_ms": round(best[2], 4), "vs_unfused": round(best[1] / best[0], 2), "vs_float32": round(best[2] / best[0], 2),
+                          "TFLOPs": round(4.0 * nb * S * T * D / best[0] / 1e9, 1), "runs_ms": [[round(x, 4) for x in r] for r in runs]}), flush=True)
+
+
 def main():
     ffi.init(0)
     lib = ffi.lib()
     if sys.argv[1:] == ["half"]:  # the float16 rows only
         return half_rows(lib)
+    if sys.argv[1:] == ["attention"]:
+        return attention_rows(lib)
     shapes = [
         ("float32", 1, 4096, 4096, 4096), ("float32", 1, 8192, 8192, 1024), ("float32", 512, 256, 256, 256),
         ("float32", 64, 1024, 1024, 256), ("float64", 1, 4096, 4096, 4096), ("float32", 1, 64, 2048, 1024),
