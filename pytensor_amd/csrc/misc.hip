@@ -49,7 +49,15 @@ __global__ void searchsorted_kernel(const void* __restrict__ x, int xdt, long lo
                                     long long* __restrict__ out) {
   for (long long j = (long long)blockIdx.x * blockDim.x + threadIdx.x; j < m; j += (long long)gridDim.x * blockDim.x) {
     long long lo = 0, hi = n;
-    if (as_int) {
+    if (as_int == 2) {
+      // a uint64 operand, the other unsigned or bool: load_l keeps the bits (and a narrower value is never negative)
+      const unsigned long long key = (unsigned long long)load_l(v, vdt, j);
+      while (lo < hi) {
+        const long long mid = lo + ((hi - lo) >> 1);
+        const unsigned long long xe = (unsigned long long)load_l(x, xdt, sorter ? sorter[mid] : mid);
+        if (right ? !(key < xe) : (xe < key)) lo = mid + 1; else hi = mid;
+      }
+    } else if (as_int) {
       const long long key = load_l(v, vdt, j);
       while (lo < hi) {
         const long long mid = lo + ((hi - lo) >> 1);
@@ -110,7 +118,11 @@ extern "C" int pthip_searchsorted(int x_dtype, int64_t n, const void* x, const v
   PTHIP_REQUIRE_INIT();
   if (m <= 0) return 0;
   auto is_float = [](int dt) { return dt == PTHIP_F64 || dt == PTHIP_F32 || dt == PTHIP_F16; };
-  const int as_int = !is_float(x_dtype) && !is_float(v_dtype);
+  auto is_signed = [](int dt) { return dt == PTHIP_I64 || dt == PTHIP_I32 || dt == PTHIP_I16 || dt == PTHIP_I8; };
+  // NumPy compares in the promoted type of the pair: float64 for a float with anything and for uint64 with a signed
+  // integer (0), uint64 for uint64 with an unsigned integer or bool (2), int64 holds every other integer pair (1)
+  int as_int = !is_float(x_dtype) && !is_float(v_dtype);
+  if (as_int && (x_dtype == PTHIP_U64 || v_dtype == PTHIP_U64)) as_int = (is_signed(x_dtype) || is_signed(v_dtype)) ? 0 : 2;
   PTHIP_KLAUNCH(searchsorted_kernel, dim3(grid_for(m)), dim3(256), 0, pthip::ctx().stream, x, x_dtype, (long long)n,
                 (const long long*)sorter, v, v_dtype, (long long)m, right, as_int, (long long*)out);
   return pthip::post_launch("searchsorted");
