@@ -18,16 +18,17 @@
 //   K-contiguous operand  -> image [row][k], leading dimension 18 elements
 //   M/N-contiguous operand-> image [k][row], leading dimension 144 (f64) / 128 (f32)
 // Tile ids are remapped so that the 8 XCDs (block b runs on XCD b%8) each walk a
-// contiguous band of tile rows (L2 reuse of the A panel).
+// contiguous band of tile rows (L2 reuse of the A panel): mfma::xcd_band.
 #include "common.h"
+#include "mfma_tile_device.h"
 
 namespace {
 
+using mfma::double4_t;
+using mfma::float16_t;
+
 constexpr int BLOCK = 256;
 constexpr int BM = 128, BN = 128, BK = 16;
-
-typedef double double4_t __attribute__((ext_vector_type(4)));
-typedef float float16_t __attribute__((ext_vector_type(16)));
 
 // ---------------------------------------------------------------------------------
 // staging: global -> registers -> LDS
@@ -125,7 +126,7 @@ template <bool KC, int BKT> struct Stage<float, KC, BKT> {
 #pragma unroll
     for (int p = 0; p < NV; p++) {
       const int id = threadIdx.x + p * BLOCK;
-      long long row, k, se;  // se: element stride between the 4 vector components
+      long long row, k;
       const float* g;
       bool full;
       if constexpr (KC) {
@@ -149,7 +150,6 @@ template <bool KC, int BKT> struct Stage<float, KC, BKT> {
         v[p].z = (k < K && row + 2 < rows) ? g[2] : 0.f;
         v[p].w = (k < K && row + 3 < rows) ? g[3] : 0.f;
       }
-      (void)se;
     }
   }
   __device__ __forceinline__ void store(float* __restrict__ s) const {
@@ -179,18 +179,9 @@ template <bool KC, int BKT> struct Stage<float, KC, BKT> {
 
 __device__ __forceinline__ void tile_coords(long long tiles_m, long long tiles_n, long long& tm,
                                             long long& tn, long long& bz) {
-  // XCD-aware remap over the whole (batch x tile) space: workgroups are dispatched x-fastest and
-  // block L runs on XCD L % 8, so XCD x gets the contiguous range [x*total/8, (x+1)*total/8) of
-  // (batch, tile) pairs — the tiles of one matrix, and the tiles of one band of a big matrix,
-  // share an L2.  (Round 1 remapped the tiles of one matrix only: the four 128x128 tiles of a
-  // 256x256 batch item landed on four XCDs and every operand was fetched from HBM twice.)
+  // the remap runs over the whole (batch x tile) space
   const long long nt = tiles_m * tiles_n;
-  long long pid = blockIdx.x + nt * (long long)blockIdx.z;
-  const long long total = nt * (long long)gridDim.z;
-  if (total % 8 == 0) {
-    const long long per = total / 8;
-    pid = (pid % 8) * per + pid / 8;
-  }
+  long long pid = mfma::xcd_band(blockIdx.x + nt * (long long)blockIdx.z, nt * (long long)gridDim.z);
   bz = pid / nt;
   pid -= bz * nt;
   tm = pid / tiles_n;
@@ -233,10 +224,7 @@ __global__ __launch_bounds__(BLOCK, 2) void dgemm_kernel(
   constexpr int WT = TILE / 2;  // wave tile edge of the 2 x 2 wave layout
   const int wm0 = SKINNY ? 0 : (w >> 1) * WT, wn0 = SKINNY ? w * 32 : (w & 1) * WT;
   double4_t acc[NI][NJ];
-#pragma unroll
-  for (int i = 0; i < NI; i++)
-#pragma unroll
-    for (int j = 0; j < NJ; j++) acc[i][j] = (double4_t){0.0, 0.0, 0.0, 0.0};
+  mfma::zero_acc(acc);
   SA sa;
   SB sb;
   const long long kb = (long long)blockIdx.y * kchunk;
@@ -274,7 +262,6 @@ __global__ __launch_bounds__(BLOCK, 2) void dgemm_kernel(
     }
     __syncthreads();
   }
-  // epilogue: D reg r -> row (l>>4) + 4r, col l&15
   const bool has_c = !split && (beta != 0.0) && C != nullptr;
   if (has_c) C += bz * sCb;
   if (split) alpha = 1.0;
@@ -284,8 +271,8 @@ __global__ __launch_bounds__(BLOCK, 2) void dgemm_kernel(
     for (int j = 0; j < NJ; j++)
 #pragma unroll
       for (int r = 0; r < 4; r++) {
-        const long long row = m0 + wm0 + i * 16 + (lane >> 4) + 4 * r;
-        const long long col = n0 + wn0 + j * 16 + (lane & 15);
+        const long long row = mfma::acc16_row(m0 + wm0 + i * 16, r, lane);
+        const long long col = mfma::acc16_col(n0 + wn0 + j * 16, lane);
         if (row < M && col < N) {
           double v = alpha * acc[i][j][r];
           if (has_c) v += beta * C[row * sC0 + col * sC1];
@@ -325,12 +312,7 @@ __global__ __launch_bounds__(BLOCK, 2) void sgemm_kernel(
   constexpr int NJ = SKINNY ? 1 : 2;
   const int wm0 = SKINNY ? 0 : (w >> 1) * 64, wn0 = SKINNY ? w * 32 : (w & 1) * 64;
   float16_t acc[2][NJ];
-#pragma unroll
-  for (int i = 0; i < 2; i++)
-#pragma unroll
-    for (int j = 0; j < NJ; j++)
-#pragma unroll
-      for (int r = 0; r < 16; r++) acc[i][j][r] = 0.f;
+  mfma::zero_acc(acc);
   SA sa;
   SB sb;
   const long long kb = (long long)blockIdx.y * kchunk;
@@ -344,18 +326,7 @@ __global__ __launch_bounds__(BLOCK, 2) void sgemm_kernel(
       for (int i = 0; i < 2; i++) af[i] = SA::frag2(as, wm0 + i * 32, kk, lane);
 #pragma unroll
       for (int j = 0; j < NJ; j++) bf[j] = SB::frag2(bs, wn0 + j * 32, kk, lane);
-      // two passes so that consecutive MFMAs never share an accumulator (a dependent
-      // back-to-back pair stalls the matrix pipe: 98 -> 102 TFLOP/s at 4096^3)
-#pragma unroll
-      for (int i = 0; i < 2; i++)
-#pragma unroll
-        for (int j = 0; j < NJ; j++)
-          acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x2f32(af[i].x, bf[j].x, acc[i][j], 0, 0, 0);
-#pragma unroll
-      for (int i = 0; i < 2; i++)
-#pragma unroll
-        for (int j = 0; j < NJ; j++)
-          acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x2f32(af[i].y, bf[j].y, acc[i][j], 0, 0, 0);
+      mfma::kstep_f32(acc, af, bf);
     }
   };
   constexpr int PRE = 4;
@@ -414,8 +385,8 @@ __global__ __launch_bounds__(BLOCK, 2) void sgemm_kernel(
     for (int j = 0; j < NJ; j++)
 #pragma unroll
       for (int r = 0; r < 16; r++) {
-        const long long row = m0 + wm0 + i * 32 + (r & 3) + 8 * (r >> 2) + 4 * (lane >> 5);
-        const long long col = n0 + wn0 + j * 32 + (lane & 31);
+        const long long row = mfma::acc32_row(m0 + wm0 + i * 32, r, lane);
+        const long long col = mfma::acc32_col(n0 + wn0 + j * 32, lane);
         if (row < M && col < N) {
           float v = alpha * acc[i][j][r];
           if (has_c) v += beta * C[row * sC0 + col * sC1];
@@ -457,11 +428,7 @@ __global__ __launch_bounds__(BLOCK, 2) void sgemm_persistent_kernel(
   const int wm0 = (w >> 1) * 64, wn0 = (w & 1) * 64;
   const long long nk = (K + BKT - 1) / BKT;
   auto coords = [&](long long L, long long& m0, long long& n0, long long& bz) {
-    long long pid = L;
-    if (total % 8 == 0) {  // XCD x walks the contiguous range [x*total/8, (x+1)*total/8)
-      const long long per = total / 8;
-      pid = (L % 8) * per + L / 8;
-    }
+    long long pid = mfma::xcd_band(L, total);
     bz = pid / nt;
     pid -= bz * nt;
     m0 = (pid / tiles_n) * BM;
@@ -486,12 +453,7 @@ __global__ __launch_bounds__(BLOCK, 2) void sgemm_persistent_kernel(
     long long m1 = 0, n1 = 0, b1 = 0;
     if (has_next) coords(Ln, m1, n1, b1);
     float16_t acc[2][2];
-#pragma unroll
-    for (int i = 0; i < 2; i++)
-#pragma unroll
-      for (int j = 0; j < 2; j++)
-#pragma unroll
-        for (int r = 0; r < 16; r++) acc[i][j][r] = 0.f;
+    mfma::zero_acc(acc);
     const float* Ab = A + bz * sAb;
     const float* Bb = B + bz * sBb;
     for (long long kt = 0; kt < nk; kt++) {
@@ -537,16 +499,7 @@ __global__ __launch_bounds__(BLOCK, 2) void sgemm_persistent_kernel(
         }
         // (without the fences the machine scheduler sinks each read back next to its use)
         __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-        for (int i = 0; i < 2; i++)
-#pragma unroll
-          for (int j = 0; j < 2; j++)
-            acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x2f32(af[cs][i].x, bf[cs][j].x, acc[i][j], 0, 0, 0);
-#pragma unroll
-        for (int i = 0; i < 2; i++)
-#pragma unroll
-          for (int j = 0; j < 2; j++)
-            acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x2f32(af[cs][i].y, bf[cs][j].y, acc[i][j], 0, 0, 0);
+        mfma::kstep_f32(acc, af[cs], bf[cs]);
         __builtin_amdgcn_sched_barrier(0);
       }
       if ((more || has_next) && DIAG < 2) {
@@ -567,8 +520,8 @@ __global__ __launch_bounds__(BLOCK, 2) void sgemm_persistent_kernel(
         for (int j = 0; j < 2; j++)
 #pragma unroll
           for (int r = 0; r < 16; r++) {
-            const long long row = m0 + wm0 + i * 32 + (r & 3) + 8 * (r >> 2) + 4 * (lane >> 5);
-            const long long col = n0 + wn0 + j * 32 + (lane & 31);
+            const long long row = mfma::acc32_row(m0 + wm0 + i * 32, r, lane);
+            const long long col = mfma::acc32_col(n0 + wn0 + j * 32, lane);
             ob[row * ldo + col] = alpha * acc[i][j][r];
           }
     } else {
@@ -578,8 +531,8 @@ __global__ __launch_bounds__(BLOCK, 2) void sgemm_persistent_kernel(
         for (int j = 0; j < 2; j++)
 #pragma unroll
           for (int r = 0; r < 16; r++) {
-            const long long row = m0 + wm0 + i * 32 + (r & 3) + 8 * (r >> 2) + 4 * (lane >> 5);
-            const long long col = n0 + wn0 + j * 32 + (lane & 31);
+            const long long row = mfma::acc32_row(m0 + wm0 + i * 32, r, lane);
+            const long long col = mfma::acc32_col(n0 + wn0 + j * 32, lane);
             if (row < M && col < N) {
               float v = alpha * acc[i][j][r];
               if (has_c) v += beta * Cb[row * sC0 + col * sC1];
@@ -630,12 +583,8 @@ __global__ __launch_bounds__(BLOCK, 1) void sgemm256_kernel(
   auto coords = [&](long long L, long long& m0, long long& n0, long long& bz) {
     // (32-bit arithmetic: the tile count of anything that fits in HBM is far below 2^31, and a 64-bit
     //  division is a few hundred instructions per tile in front of the first MFMA)
-    const unsigned tot = (unsigned)total, ntu = (unsigned)nt, tnu = (unsigned)tiles_n;
-    unsigned pid = (unsigned)L;
-    if (tot % 8 == 0) {  // XCD x walks the contiguous range [x*total/8, (x+1)*total/8)
-      const unsigned per = tot / 8;
-      pid = (pid % 8) * per + pid / 8;
-    }
+    const unsigned ntu = (unsigned)nt, tnu = (unsigned)tiles_n;
+    unsigned pid = mfma::xcd_band((unsigned)L, (unsigned)total);
     const unsigned b = pid / ntu;
     pid -= b * ntu;
     bz = b;
@@ -711,6 +660,7 @@ __global__ __launch_bounds__(BLOCK, 1) void sgemm256_kernel(
     long long m1 = 0, n1 = 0, b1 = 0;
     if (has_next) coords(Ln, m1, n1, b1);
     float16_t acc[4][4];
+    // (written out: mfma::zero_acc beside mfma::kstep_f32 changed this kernel's scratch, profiles/gemm_tile_header.md)
 #pragma unroll
     for (int i = 0; i < 4; i++)
 #pragma unroll
@@ -754,16 +704,7 @@ __global__ __launch_bounds__(BLOCK, 1) void sgemm256_kernel(
           for (int j = 0; j < 4; j++) bf[ns][j] = bfrag(j, kk + 1);
         }
         __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-        for (int i = 0; i < 4; i++)
-#pragma unroll
-          for (int j = 0; j < 4; j++)
-            acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x2f32(af[cs][i].x, bf[cs][j].x, acc[i][j], 0, 0, 0);
-#pragma unroll
-        for (int i = 0; i < 4; i++)
-#pragma unroll
-          for (int j = 0; j < 4; j++)
-            acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x2f32(af[cs][i].y, bf[cs][j].y, acc[i][j], 0, 0, 0);
+        mfma::kstep_f32(acc, af[cs], bf[cs]);
         __builtin_amdgcn_sched_barrier(0);
       }
       } else {
@@ -774,29 +715,21 @@ __global__ __launch_bounds__(BLOCK, 1) void sgemm256_kernel(
         for (int i = 0; i < 4; i++) af[i] = afrag(i, kk);
 #pragma unroll
         for (int j = 0; j < 4; j++) bf[j] = bfrag(j, kk);
-#pragma unroll
-        for (int i = 0; i < 4; i++)
-#pragma unroll
-          for (int j = 0; j < 4; j++)
-            acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x2f32(af[i].x, bf[j].x, acc[i][j], 0, 0, 0);
-#pragma unroll
-        for (int i = 0; i < 4; i++)
-#pragma unroll
-          for (int j = 0; j < 4; j++)
-            acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x2f32(af[i].y, bf[j].y, acc[i][j], 0, 0, 0);
+        mfma::kstep_f32(acc, af, bf);
       }
       }
       if (more || has_next) T2_SSTORE(As + (buf ^ 1) * ASZ, Bs + (buf ^ 1) * BSZ);
       __syncthreads();
       buf ^= 1;
     }
+    // hand-shaped addressing: the lane's share of the row and column sits in ob, a register adds its share of the row
     float* ob = out + bz * M * N + (m0 + wm0 + 4 * h) * ldo + n0 + wn0 + i32;
     if (!has_c) {
 #pragma unroll
       for (int i = 0; i < 4; i++)
 #pragma unroll
         for (int r = 0; r < 16; r++) {
-          float* orow = ob + (long long)(i * 32 + (r & 3) + 8 * (r >> 2)) * ldo;
+          float* orow = ob + (long long)mfma::acc32_reg_row(i * 32, r) * ldo;
 #pragma unroll
           for (int j = 0; j < 4; j++) orow[j * 32] = alpha * acc[i][j][r];
         }
@@ -808,9 +741,9 @@ __global__ __launch_bounds__(BLOCK, 1) void sgemm256_kernel(
         for (int j = 0; j < 4; j++)
 #pragma unroll
           for (int r = 0; r < 16; r++) {
-            const long long row = m0 + wm0 + i * 32 + (r & 3) + 8 * (r >> 2) + 4 * h;
+            const long long row = mfma::acc32_reg_row(m0 + wm0 + i * 32, r) + 4 * h;
             const long long col = n0 + wn0 + j * 32 + i32;
-            ob[(long long)(i * 32 + (r & 3) + 8 * (r >> 2)) * ldo + j * 32] = alpha * acc[i][j][r] + beta * Cb[row * sC0 + col * sC1];
+            ob[(long long)mfma::acc32_reg_row(i * 32, r) * ldo + j * 32] = alpha * acc[i][j][r] + beta * Cb[row * sC0 + col * sC1];
           }
     }
     if (!has_next) break;
@@ -931,7 +864,7 @@ int launch(long long batch, long long M, long long N, long long K, T alpha, cons
     if constexpr (sizeof(T) == 4 && !SKINNY && BKT == 32) {
       // 256-aligned M, N (any operand orientation since round 4): one 256 x 256 tile per workgroup
       static const bool big = !(getenv("PTHIP_SGEMM_256") && atoi(getenv("PTHIP_SGEMM_256")) == 0);
-      if (big && M % T2 == 0 && N % T2 == 0 && K % T2K == 0 && K >= T2K && vecA && vecB && (ldo % 1 == 0)) {
+      if (big && M % T2 == 0 && N % T2 == 0 && K % T2K == 0 && K >= T2K && vecA && vecB) {
         const size_t sh = (size_t)(2 * (AKC ? T2 * T2ALD : T2K * T2) + 2 * (BKC ? T2 * T2ALD : T2K * T2)) * sizeof(float);
         static const bool pf = !(getenv("PTHIP_SGEMM_256_PF") && atoi(getenv("PTHIP_SGEMM_256_PF")) == 0);
         auto k256 = pf ? sgemm256_kernel<true, AKC, BKC> : sgemm256_kernel<false, AKC, BKC>;
@@ -954,8 +887,6 @@ int launch(long long batch, long long M, long long N, long long K, T alpha, cons
                       (const float*)C, M, N, K, lda, ldb, sAb, sBb, sCb, sC0, sC1, (float)alpha, (float)beta, t_m, t_n, batch, ldo);
         return pthip::post_launch("gemm(256x256)");
       }
-    }
-    if constexpr (sizeof(T) == 4 && !SKINNY && BKT == 32) {
       // more tiles than resident workgroups: the persistent kernel (prologues / epilogues of
       // consecutive tiles overlap).  PTHIP_SGEMM_PERSIST=0 keeps one tile per workgroup.
       static const bool persist = !(getenv("PTHIP_SGEMM_PERSIST") && atoi(getenv("PTHIP_SGEMM_PERSIST")) == 0);

@@ -34,6 +34,7 @@
 // Epilogue: a lane holds a column of O^T, so the 128 x Dv tile is transposed through the (now free) LDS and stored as
 // 16-byte rows.
 #include "common.h"
+#include "mfma_tile_device.h"
 
 namespace {
 
@@ -43,8 +44,8 @@ constexpr int KT = 64;        // keys per tile
 constexpr int VLD = KT + 4;   // pitch of the V^T tile in halves
 constexpr int MAX_D = 128;
 
-typedef _Float16 half8_t __attribute__((ext_vector_type(8)));
-typedef float float16_t __attribute__((ext_vector_type(16)));
+using mfma::float16_t;
+using mfma::half8_t;
 typedef unsigned short hbits;
 
 union Vec8 {
@@ -97,8 +98,7 @@ __global__ __launch_bounds__(BLOCK, 2) void hattention_kernel(
   hbits* Ks = (hbits*)smem_raw;   // [2][KSIZE]
   hbits* Vs = Ks + 2 * KSIZE;     // [2][VSIZE]
   const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6, h = lane >> 5, c = lane & 31;
-  long long pid = blockIdx.x;
-  if (total % 8 == 0) pid = (pid % 8) * (total / 8) + pid / 8;  // the query blocks of an item share an XCD's L2 (hgemm.hip)
+  const long long pid = mfma::xcd_band((long long)blockIdx.x, total);  // the query blocks of an item share an XCD's L2
   const long long b = pid / qblocks, q0 = (pid - b * qblocks) * QB;
   const hbits* Qb = Q + b * sQb;
   const hbits* Kb = K + b * sKb;
@@ -177,10 +177,7 @@ __global__ __launch_bounds__(BLOCK, 2) void hattention_kernel(
   };
 
   float16_t oacc[NO];
-#pragma unroll
-  for (int i = 0; i < NO; i++)
-#pragma unroll
-    for (int r = 0; r < 16; r++) oacc[i][r] = 0.f;
+  mfma::zero_acc(oacc);
   float m = -__builtin_huge_valf(), l = 0.f;  // this lane's query: running maximum (both lane halves agree), sum of its own keys
 
   load_tile(0);
@@ -196,10 +193,7 @@ __global__ __launch_bounds__(BLOCK, 2) void hattention_kernel(
     const hbits* vs = Vs + buf * VSIZE;
     // S^T (64 keys x 32 queries of this wave) = K Q^T
     float16_t sacc[2];
-#pragma unroll
-    for (int kb = 0; kb < 2; kb++)
-#pragma unroll
-      for (int r = 0; r < 16; r++) sacc[kb][r] = 0.f;
+    mfma::zero_acc(sacc);
 #pragma unroll
     for (int kk = 0; kk < ND; kk++) {
       if (kk * 16 < D || kk == 0) {  // (uniform: k-steps of zero fill only are skipped)
@@ -219,7 +213,7 @@ __global__ __launch_bounds__(BLOCK, 2) void hattention_kernel(
 #pragma unroll
       for (int r = 0; r < 16; r++) {
         float s = sacc[kb][r] * sl2;
-        if (tail && key0 + kb * 32 + (r & 3) + 8 * (r >> 2) + 4 * h >= T) s = -__builtin_huge_valf();
+        if (tail && mfma::acc32_row(key0 + kb * 32, r, lane) >= T) s = -__builtin_huge_valf();
         sacc[kb][r] = s;
         mx = fmaxf(mx, s);
       }

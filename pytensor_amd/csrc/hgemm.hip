@@ -6,7 +6,7 @@
 // overflow to inf, gradual underflow) happens in registers in the epilogue.
 //
 // MFMA 32x32x16 f16: lane l passes 8 halves of A (row l&31, k = 8(l>>5) .. +7) and 8 of B (the same k, column l&31);
-// the accumulator layout is the one of the fp32 32x32x2 form (gemm.hip): D reg r -> row (r&3)+8(r>>2)+4(l>>5), col l&31.
+// the accumulator layout is the one of the fp32 32x32x2 form (mfma_tile_device.h: acc32_row, acc32_col).
 // The sum over k is order-free, so all the kernel has to guarantee is that the A and the B fragment of a lane hold the
 // SAME eight k values: both are read from LDS at k = 16 kk + 8 (l>>5).
 //
@@ -40,6 +40,7 @@
 // last, so the bits do not depend on the arrival order — rounds once and stores through the epilogue.  Nobody waits:
 // a workgroup that is not last goes on to its next unit.  hgemm_splits() holds the rule for S.
 #include "common.h"
+#include "mfma_tile_device.h"
 #include "wave_device.h"
 
 namespace {
@@ -49,8 +50,8 @@ constexpr int HN = 128;         // tile columns
 constexpr int HK = 64;          // k per stage
 constexpr int HLD = HK + 8;     // LDS row pitch in halves (see above)
 
-typedef _Float16 half8_t __attribute__((ext_vector_type(8)));
-typedef float float16_t __attribute__((ext_vector_type(16)));
+using mfma::float16_t;
+using mfma::half8_t;
 typedef unsigned short hbits;  // a half moved as bits
 
 union Vec8 {
@@ -175,11 +176,7 @@ __global__ __launch_bounds__(BLOCK, 2) void hgemm_kernel(
   const long long nk = K > 0 ? (K + HK - 1) / HK : 1;  // K = 0: one stage of zero fill
   // unit L: its tile origin, batch item, unit id u = (bz * nt + tile) * S + s and stage range [kt0, kt1)
   auto coords = [&](long long L, long long& m0, long long& n0, long long& bz, long long& u, long long& kt0, long long& kt1) {
-    long long pid = L;
-    if (total % 8 == 0) {  // XCD x (workgroup L runs on XCD L % 8) walks the contiguous range [x*total/8, (x+1)*total/8)
-      const long long per = total / 8;
-      pid = (L % 8) * per + L / 8;
-    }
+    long long pid = mfma::xcd_band(L, total);
     u = pid;
     kt0 = 0;
     kt1 = nk;
@@ -212,12 +209,7 @@ __global__ __launch_bounds__(BLOCK, 2) void hgemm_kernel(
     long long m1 = 0, n1 = 0, b1 = 0, u1 = 0, kn0 = 0, kn1 = 0;
     if (has_next) coords(Ln, m1, n1, b1, u1, kn0, kn1);
     float16_t acc[2][NJ];
-#pragma unroll
-    for (int i = 0; i < 2; i++)
-#pragma unroll
-      for (int j = 0; j < NJ; j++)
-#pragma unroll
-        for (int r = 0; r < 16; r++) acc[i][j][r] = 0.f;
+    mfma::zero_acc(acc);
     const hbits* Ab = A + bz * sAb;
     const hbits* Bb = B + bz * sBb;
     // (constants in the unsplit kernel, which then compiles to the registers and spills it had before there were units)
@@ -292,8 +284,8 @@ __global__ __launch_bounds__(BLOCK, 2) void hgemm_kernel(
         for (int j = 0; j < NJ; j++)
 #pragma unroll
           for (int r = 0; r < 16; r++) {
-            const long long row = m0 + wm0 + i * 32 + (r & 3) + 8 * (r >> 2) + 4 * (lane >> 5);
-            const long long col = n0 + wn0 + j * 32 + (lane & 31);
+            const long long row = mfma::acc32_row(m0 + wm0 + i * 32, r, lane);
+            const long long col = mfma::acc32_col(n0 + wn0 + j * 32, lane);
             if (interior || (row < M && col < N)) ob[row * N + col] = to_half_bits(acc[i][j][r]);
           }
     }
@@ -347,8 +339,6 @@ int hgemm_launch(long long batch, long long M, long long N, long long K, const h
   if (S > 1) {
     if (int r = mem.alloc((size_t)total * TM * HN * sizeof(float), &slabs)) return r;
     if (int r = pthip_ticket_slots((int)tiles, &tickets)) return r;
-  }
-  if (S > 1) {
     const HSplitArgs<true> sp{(int)S, (float*)slabs, (int*)tickets};
     PTHIP_KLAUNCH((hgemm_kernel<AKC, BKC, SKINNY, true>), dim3((unsigned)grid), dim3(BLOCK), shmem, pthip::ctx().stream, out, A, B, M, N,
                   K, lda, ldb, sAb, sBb, tiles_m, tiles_n, batch, vecA, vecB, sp);
